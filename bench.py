@@ -16,7 +16,19 @@ and exits non-zero if any child fails.  Under ``torch.distributed.run`` the envi
 A step = one pass of the hot path over one batch of B events already resident in HBM:
 layer-1 k-NN build, global variables, 4x(P|Q GEMM, fused EdgeConv, re-kNN), post MLP, pooling,
 readout, energy head, LogCosh, full backward, one flat RCCL all-reduce (N > 1), Adam step.
-Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` and `cpu_baseline`.
+Rank 0 prints ONE JSON line.
+
+A plain run does what the headline figure needs and nothing else: set-up, ramp-up, W warm-up steps, the K timed
+steps, the result line (``metric``, ``value``, ``unit``, ``higher_is_better``, ``dtype``, ``ms_per_step`` = the
+milliseconds one timed step took, and the facts of the timed region itself).  ``--full`` adds every other measurement
+and check to the same line: clock samples and graph ties of the timed region, the config-3 facts (replica equality,
+all-reduce cost), per-op HIP-event timers with `roofline` / `path_roofline`, a second batch size, the fp32 mode, the
+library yardsticks and `cpu_baseline` with the in-run parity gate (exit code 3 when it fails).
+
+``--dump-outputs DIR`` writes what the LAST timed step handed to its caller as ``DIR/<name>.npy`` (float32):
+``prediction`` (the task output per event), ``loss``, ``grad`` (the flat gradient after the all-reduce) and ``weights``
+(every parameter after the optimizer step, flattened in ``parameters()`` order).  Inputs and initial weights are
+seeded and the number of steps before the timed region is fixed in such a run, so two builds compare array for array.
 """
 import argparse
 import json
@@ -36,6 +48,8 @@ PEAK_BF16_TFLOPS = 2500.0      # dense bf16 MFMA peak, /opt/skills/guides/MI355X
 PEAK_F32_TFLOPS = 157.3
 RAMP_UP_STEPS = 80             # untimed steps before the W warm-up steps, at least (clock / allocator ramp: ramp_up())
 RAMP_UP_MAX_S = float(os.environ.get("GN_BENCH_RAMP_MAX_S", "20"))   # ... and at most this long while the step time still moves
+RAMP_UP_MAX_S_PLAIN = 10.0     # ... in a plain run (no --full), whose time outside the steps is part of its cost
+DUMP_MAX_BYTES = 64 << 20      # --dump-outputs: all arrays together
 TRAFFIC_FILE = os.path.join("profiles", os.environ.get("GN_TRAFFIC_FILE", "r03_traffic.json"))
 
 
@@ -527,6 +541,20 @@ def kernel_source_hash() -> str:
     return h.hexdigest()[:16]
 
 
+def write_outputs(directory: str, tensors: dict) -> None:
+    """``--dump-outputs``: every tensor as ``<directory>/<name>.npy`` in float32, ``DUMP_MAX_BYTES`` in all.  An array
+    over its share of that budget is stored as a fixed sample of its flattened elements (indices drawn once from a
+    generator seeded with the element count, ascending), so the same elements are kept in every run."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_MAX_BYTES // 4 // max(len(tensors), 1)                 # elements per array
+    for name, t in tensors.items():
+        a = t.detach().to(torch.float32).cpu().numpy()
+        if a.size > share:
+            keep = np.sort(np.random.default_rng(a.size).choice(a.size, size=share, replace=False))
+            a = a.reshape(-1)[keep]
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a))
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -550,10 +578,17 @@ def main():
     ap.add_argument("--cpu-warmup", type=int, default=3)
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / rendezvous / all-reduce control flow only, on CPU over gloo (no kernels, value null)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: clock samples, graph ties, config-3 facts, per-op timers and "
+                         "roofline, other batch size, fp32 mode, library yardsticks, CPU baseline with the parity gate")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (prediction, loss, grad, weights) as DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:], args.dry_run))      # nothing above touched the GPU
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -585,7 +620,7 @@ def main():
         else:
             dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
 
-    from graphnet_amd import _lib, ops
+    from graphnet_amd import _lib
     from graphnet_amd.parallel import FlatGradAllReduce, broadcast_parameters
     from graphnet_amd.synthetic import synthetic_icecube86_batch
     _lib.lib()                                           # fail loudly if the HIP library is missing
@@ -625,14 +660,19 @@ def main():
     # power-state ramp and allocator growth: 10.0 ms/step with 5 warm-up steps vs 7.5 ms/step with 40), so a short
     # warm-up would time the ramp instead of the steady state - see ramp_up().
     _log(f"rank {rank}/{world}: {args.events} events = {n_nodes} pulses per GPU; ramp-up + warm-up")
-    ramp = ramp_up(step, world, dev, RAMP_UP_STEPS, RAMP_UP_MAX_S)
+    # --dump-outputs: exactly RAMP_UP_STEPS, so that the timed region starts from the same weights in every run
+    ramp_max_s = 0.0 if args.dump_outputs else RAMP_UP_MAX_S if args.full else min(RAMP_UP_MAX_S, RAMP_UP_MAX_S_PLAIN)
+    ramp = ramp_up(step, world, dev, RAMP_UP_STEPS, ramp_max_s)
     if rank == 0:
         _log(f"ramp-up: {ramp['steps']} steps in {ramp['seconds']:.1f} s, ms/step per block of 10: {ramp['block_ms_per_step']}")
     for _ in range(args.warmup):
         step()
     fence()
     mem0 = torch.cuda.memory_stats(dev)
-    sampler = ClockSampler(dev).start()
+    sampler = ClockSampler(dev).start() if args.full else None
+    last_pred = []
+    if args.dump_outputs:                            # keeps the task output of the step that ran last
+        model._tasks[0].register_forward_hook(lambda _m, _i, o: last_pred.__setitem__(slice(None), [o]))
     step_ev = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
     host_ms = []
     t0 = time.perf_counter()
@@ -644,8 +684,13 @@ def main():
         host_ms.append(1e3 * (time.perf_counter() - th0))
     fence()
     dt = time.perf_counter() - t0
-    sampler.stop()
+    if sampler is not None:
+        sampler.stop()
     mem1 = torch.cuda.memory_stats(dev)
+    if args.dump_outputs and rank == 0:             # before anything below steps the model again
+        write_outputs(args.dump_outputs, {
+            "prediction": last_pred[0], "loss": loss.reshape(1), "grad": sync.flat,
+            "weights": torch.cat([p.detach().reshape(-1) for p in model.parameters()])})
     step_ms = [a.elapsed_time(b) for a, b in zip(step_ev[:-1], step_ev[1:])]
     sm = sorted(step_ms)
     med = sm[len(sm) // 2]
@@ -659,16 +704,75 @@ def main():
         "allocator": {k: int(mem1.get(k, 0)) - int(mem0.get(k, 0)) for k in
                       ("num_alloc_retries", "num_device_alloc", "num_device_free", "num_sync_all_streams", "num_ooms")},
         "reserved_gb": mem1.get("reserved_bytes.all.current", 0) / 1e9,
-        "clock": sampler.summary(),
         # the step time depends on the training state: Adam steps on the one synthetic batch make the learned k-NN
         # coordinates collapse onto shared values, the graphs of layers 3-4 fill with distance ties ((k+1)-th neighbours
         # = overflow rows, hub sources) and the data-dependent kernels grow (6.4 -> 6.9 ms/step at B = 1024
         # from ~250 optimizer steps on).  Two runs compare only at the same number of steps taken before the timed region.
         "optimizer_steps_before": ramp["steps"] + args.warmup,
-        "graph_ties_after": graph_ties(model, batch),
     }
+    tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
+    if world > 1:
+        dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
+    dt = float(tmax.item())
     if rank == 0:
-        _log(f"timed region: {1e3 * dt / args.steps:.2f} ms/step; per-op timers, other batch sizes and modes next")
+        _log(f"timed region: {1e3 * dt / args.steps:.2f} ms/step" +
+             ("; per-op timers, other batch sizes and modes next" if args.full else ""))
+    final_loss = float(loss.detach())
+    more = None
+    if args.full:
+        timed_region["clock"] = sampler.summary()
+        timed_region["graph_ties_after"] = graph_ties(model, batch)
+        more = full_measurements(args, model, sync, opt, batch, eager_step, fence, dev, rank, world, dt)
+
+    exit_code = 0
+    if rank == 0:
+        out = {
+            "metric": "events/sec DynEdge fwd+bwd, IceCube-86 k=8",
+            "value": args.events * world * args.steps / dt, "unit": "events/s",
+            "n_gpus": dist.get_world_size() if world > 1 else 1,
+            "steps": args.steps, "warmup": args.warmup, "ramp_up_steps": ramp["steps"], "ramp_up": ramp,
+            "timed_region": timed_region,
+            "library": {"path": os.path.relpath(_lib.LIB_PATH, ROOT), "built_in_run": bool(_lib.BUILT_IN_PROCESS),
+                        "so_mtime": time.strftime("%Y-%m-%dT%H:%M:%SZ", time.gmtime(os.path.getmtime(_lib.LIB_PATH))),
+                        "kernel_source_hash": kernel_source_hash()},
+            "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+            "config": {"workload": ("configs[1]: DynEdge energy regression, synthetic IceCube-86 pulses "
+                                    "(~150/event, 7 features), k=8, fwd+bwd+Adam" if world == 1 else
+                                    f"configs[2]: configs[1] as event-batch data parallel over {world} GPUs, "
+                                    "RCCL gradient all-reduce"),
+                       "events_per_gpu": args.events, "global_batch": args.events * world,
+                       "pulses_per_gpu": n_nodes,
+                       "parallelism": f"dp{world} (event shards, one flat RCCL all-reduce)"},
+            "backend": (dist.get_backend() if world > 1 else None),
+            "allreduce_bytes": int(sync.flat.numel()) * 4,
+            "launch": launch, "final_loss": final_loss, "full": bool(args.full),
+            "outputs_dumped": bool(args.dump_outputs),
+        }
+        if args.full:
+            out["config"]["edges_per_layer"] = more.pop("edges_per_layer")
+            out.update(more)
+        parity_ok = out.get("cpu_baseline", {}).get("parity", {}).get("pass", True)
+        print(json.dumps(out))
+        sys.stdout.flush()
+        if not parity_ok:               # the in-run parity gate gates: a fast wrong answer is not a result
+            print("[bench] PARITY GATE FAILED against the oracle: " + json.dumps(out["cpu_baseline"]["parity"]),
+                  file=sys.stderr, flush=True)
+            exit_code = 3
+    if world > 1:
+        dist.barrier()                  # with --full rank 0 is still measuring its yardsticks: leave together
+        dist.destroy_process_group()
+    if exit_code:
+        sys.exit(exit_code)
+
+
+def full_measurements(args, model, sync, opt, batch, eager_step, fence, dev, rank: int, world: int, dt: float):
+    """``--full``, after the timed region and on the same model.  Every rank (these steps contain collectives): the
+    config-3 facts, the per-op HIP-event timers over a few eager steps, the second batch size and the fp32 mode; rank 0
+    then prices the roofline, measures the library yardsticks and the CPU baseline and returns the fields it adds to
+    the result line (other ranks: None).  ``dt``: seconds the timed region took."""
+    from graphnet_amd import ops
+    n_nodes = int(batch.x.shape[0])
     # config-3 facts (SURVEY.md 8d): replicas bitwise identical after the timed steps, cost of the exchange
     same_weights = weights_identical_across_ranks(model)
     ar_alone_us = allreduce_us(sync)
@@ -711,14 +815,8 @@ def main():
         fp32 = timed_side_run(model, sync, opt, args.fp32_events, 20241016 + 2000 + rank, dev, world, fence, 5, 8)
         fp32["dtype"] = "f32 (v_mfma_f32_32x32x2_f32, fp32 storage)"
         model.backbone.set_backend(dtype="bf16")
-    tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
-    if world > 1:
-        dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
-    dt = float(tmax.item())
-
-    exit_code = 0
+    fields = None
     if rank == 0:
-        total_events = args.events * world * args.steps
         # edges of the layer-1 graph (degree k or k+1) ~ edges of every layer
         with torch.no_grad():
             t = ops.knn_graph(batch.x, [0, 1, 2], batch.batch.to(torch.int32), batch.ptr.to(torch.int32), 8)
@@ -790,27 +888,10 @@ def main():
                                       f"{tj.get('_kernel_source_hash')}, this run has {kernel_source_hash()}")
         except Exception:
             pass
-        out = {
-            "metric": "events/sec DynEdge fwd+bwd, IceCube-86 k=8",
-            "value": total_events / dt, "unit": "events/s", "n_gpus": dist.get_world_size() if world > 1 else 1,
-            "steps": args.steps, "warmup": args.warmup, "ramp_up_steps": ramp["steps"], "ramp_up": ramp,
-            "timed_region": timed_region,
-            "library": {"path": os.path.relpath(_lib.LIB_PATH, ROOT), "built_in_run": bool(_lib.BUILT_IN_PROCESS),
-                        "so_mtime": time.strftime("%Y-%m-%dT%H:%M:%SZ", time.gmtime(os.path.getmtime(_lib.LIB_PATH))),
-                        "kernel_source_hash": kernel_source_hash()},
-            "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-            "config": {"workload": ("configs[1]: DynEdge energy regression, synthetic IceCube-86 pulses "
-                                    "(~150/event, 7 features), k=8, fwd+bwd+Adam" if world == 1 else
-                                    f"configs[2]: configs[1] as event-batch data parallel over {world} GPUs, "
-                                    "RCCL gradient all-reduce"),
-                       "events_per_gpu": args.events, "global_batch": args.events * world,
-                       "pulses_per_gpu": n_nodes, "edges_per_layer": n_edges,
-                       "parallelism": f"dp{world} (event shards, one flat RCCL all-reduce)"},
-            "backend": (dist.get_backend() if world > 1 else None),
+        fields = {
+            "edges_per_layer": n_edges,
             "allreduce_us_per_step": ar_in_step_us if world > 1 else 0.0,
             "allreduce_alone_us": ar_alone_us,
-            "allreduce_bytes": int(sync.flat.numel()) * 4,
             "weights_identical_across_ranks": same_weights,
             "roofline": {"bound": bound, "kernel": kernel_shape, "achieved": achieved, "peak": peak, "unit": unit,
                          "frac": achieved / peak, "traffic": traffic, "traffic_source": traffic_source,
@@ -830,26 +911,14 @@ def main():
             # step, ms per launch)
             "kernel_shape_ms": {k: [v[0] / prof_steps, v[1] / max(v[0], 1)]
                                 for k, v in sorted(detail.items(), key=lambda kv: -kv[1][1])},
-            "launch": launch, "host_issue_ms": host_issue_ms,
-            "final_loss": float(loss.detach()),
+            "host_issue_ms": host_issue_ms,
             "measured_peaks": (_log("yardsticks: library GEMM, device copy"), measured_peaks(dev))[1],
             "other_batch_size": extra,
             "fp32": fp32,
         }
         if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(args.cpu_events, args.cpu_steps, args.cpu_warmup, parity_model=model)
-        parity_ok = out.get("cpu_baseline", {}).get("parity", {}).get("pass", True)
-        print(json.dumps(out))
-        sys.stdout.flush()
-        if not parity_ok:               # the in-run parity gate gates: a fast wrong answer is not a result
-            print("[bench] PARITY GATE FAILED against the oracle: " + json.dumps(out["cpu_baseline"]["parity"]),
-                  file=sys.stderr, flush=True)
-            exit_code = 3
-    if world > 1:
-        dist.barrier()                  # rank 0 is still measuring its yardsticks: leave together
-        dist.destroy_process_group()
-    if exit_code:
-        sys.exit(exit_code)
+            fields["cpu_baseline"] = cpu_baseline(args.cpu_events, args.cpu_steps, args.cpu_warmup, parity_model=model)
+    return fields
 
 
 if __name__ == "__main__":

@@ -867,10 +867,18 @@ def test_particlenet_backbone(oracle, name, mode, tol):
     assert rel_err(y, yo.detach()) < tol
     if mode == 0:   # the re-clustered graph is the oracle's k-NN of the same coordinates
         assert torch.equal(forced[1], oracle.knn_graph(trace["conv_out"][0].detach().cpu(), 16, bc.batch, [0, 1, 2]))
+    # A Linear bias in front of a training-mode BatchNorm has an exactly-zero gradient (the batch mean absorbs it): both
+    # sides hold rounding noise only (bf16: the cancellation of ~1e5 rounded terms of size 1e-2).  These parameters are
+    # named by the structure of the network, not by the size of the oracle's noise, which depends on the host's CPU
+    # and thread count.
+    zero_grad = {f"_conv_layers.{l}.nn.{i}.bias" for l, conv in enumerate(ref._conv_layers)
+                 for i, (a, nxt) in enumerate(zip(conv.nn, list(conv.nn)[1:]))
+                 if isinstance(a, torch.nn.Linear) and isinstance(nxt, torch.nn.BatchNorm1d)}
+    assert len(zero_grad) == 6
     for (kn, p), (_, po) in zip(m.named_parameters(), ref.named_parameters()):
         assert p.grad is not None, kn
-        if po.grad.abs().max() < 1e-5:      # a Linear bias in front of BatchNorm has an exactly-zero gradient:
-            # both sides hold rounding noise only (bf16: the cancellation of ~1e5 rounded terms of size 1e-2)
+        if kn in zero_grad:
+            print(f"{name}: zero-gradient {kn}: device max {float(p.grad.abs().max()):.3e}, oracle max {float(po.grad.abs().max()):.3e}")
             assert p.grad.abs().max() < (1e-5 if mode == 0 else 5e-3), kn
         elif mode == 0:
             assert rel_err(p.grad, po.grad) < 2e-3, f"{name}: grad {kn}"

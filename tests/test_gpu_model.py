@@ -338,7 +338,7 @@ def test_bench_two_ranks_on_one_gpu_rehearsal():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["GN_BENCH_REHEARSE"] = "1"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--events", "128", "--steps", "3",
-                        "--warmup", "1", "--extra-events", "0", "--fp32-events", "0", "--profile-steps", "2"],
+                        "--warmup", "1", "--full", "--extra-events", "0", "--fp32-events", "0", "--profile-steps", "2"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

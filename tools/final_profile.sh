@@ -36,6 +36,8 @@ python3 tools/rocpd_stats.py $(find gpurun_out/prof_$tag/c4 -name "*.db" | head 
 rocprofv3 --kernel-trace -d gpurun_out/prof_$tag/c5 -o c5 -- python3 tools/run_config5.py 16 bf16 5 > gpurun_out/${tag}_config5_b16.log 2>&1 || exit 8
 python3 tools/rocpd_stats.py $(find gpurun_out/prof_$tag/c5 -name "*.db" | head -1) gpurun_out/${tag}_config5_kernel_stats.csv > /dev/null
 find gpurun_out/prof_$tag -name "*.db" -delete
-python3 bench.py > gpurun_out/${tag}_bench.json 2> gpurun_out/${tag}_bench.err || exit 1
+# --full: the line kept in profiles/ carries the roofline, the other batch size, the fp32 mode and the CPU baseline
+out=${GN_PROFILE_OUT:-profile_out}; mkdir -p $out
+python3 bench.py --full > $out/${tag}_bench.json 2> $out/${tag}_bench.err || exit 1
 echo "bench done"
 echo "all done"
