@@ -241,8 +241,8 @@ int gn_edgeconv_max_fwd(const int32_t* nbr, int32_t N, int32_t K, const void* PQ
     if (K < 1 || K > 16 || N < 0 || (reinterpret_cast<uintptr_t>(PQ) & 15) || (reinterpret_cast<uintptr_t>(W2p) & 15) ||
         (reinterpret_cast<uintptr_t>(saved) & 15))
         return bad("gn_edgeconv_max_fwd", "need 1<=K<=16 and 16-byte aligned PQ / W2p / saved");
-    hipError_t r = gn::launch_edge_max_fwd(make_graph(nbr, nullptr, nullptr, nullptr, N, K), PQ, H1p, W2p, b2, H2, out, ldo,
-                                           saved, S(stream));
+    hipError_t r = gn::launch_edge_fwd(1, make_graph(nbr, nullptr, nullptr, nullptr, N, K), PQ, H1p, H1p, W2p, b2, H2, out, ldo,
+                                       nullptr, nullptr, 0, saved, S(stream), 1);
     if (r == hipErrorNotSupported) return bad("gn_edgeconv_max_fwd", "shape outside the fused envelope (gn_edgeconv_max_supported)");
     return fail(r, "gn_edgeconv_max_fwd");
 }
@@ -250,8 +250,8 @@ int gn_edgeconv_max_dw2(const int32_t* nbr, int32_t N, int32_t K, const void* PQ
                         const void* gout, int64_t ldg, void* saved, float* slab, float* db2_part, void* stream) {
     if (K < 1 || K > 16 || N < 1 || H1 > H1p || (ldg & 7) || (reinterpret_cast<uintptr_t>(gout) & 15))
         return bad("gn_edgeconv_max_dw2", "bad shapes");
-    hipError_t r = gn::launch_edge_max_dw2(make_graph(nbr, nullptr, nullptr, nullptr, N, K), PQ, H1p, H1, H2, gout, ldg, saved,
-                                           slab, db2_part, S(stream));
+    hipError_t r = gn::launch_edge_dw2(1, make_graph(nbr, nullptr, nullptr, nullptr, N, K), PQ, H1p, H1, H2, gout, ldg, saved,
+                                       slab, db2_part, S(stream), 1);
     if (r == hipErrorNotSupported) return bad("gn_edgeconv_max_dw2", "shape outside the fused envelope (gn_edgeconv_max_supported)");
     return fail(r, "gn_edgeconv_max_dw2");
 }
@@ -260,8 +260,8 @@ int gn_edgeconv_max_bwd(const int32_t* nbr, int32_t N, int32_t K, int32_t H1p, i
     if (K < 1 || K > 16 || N < 0 || (ldg & 7) || (ldp & 7) || (reinterpret_cast<uintptr_t>(gout) & 15) ||
         (reinterpret_cast<uintptr_t>(dP) & 15))
         return bad("gn_edgeconv_max_bwd", "need 1<=K<=16, gout / dP 16-byte aligned with 16-byte row pitches");
-    hipError_t r = gn::launch_edge_max_bwd(make_graph(nbr, nullptr, nullptr, nullptr, N, K), H1p, H2, gout, ldg, saved, W2Tp, H2p,
-                                           dpre, dP, ldp, S(stream));
+    hipError_t r = gn::launch_edge_bwd(1, make_graph(nbr, nullptr, nullptr, nullptr, N, K), nullptr, H1p, H2, gout, ldg, saved, W2Tp,
+                                       H2p, dpre, dP, ldp, S(stream), 1, H1p);
     if (r == hipErrorNotSupported) return bad("gn_edgeconv_max_bwd", "shape outside the fused envelope (gn_edgeconv_max_supported)");
     return fail(r, "gn_edgeconv_max_bwd");
 }

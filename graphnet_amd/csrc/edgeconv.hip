@@ -26,6 +26,7 @@
 // per centre (8/16/32 >= K); the rare (K+1)-th neighbour of the k+1-then-mask semantics is an
 // "overflow" row t (centre ovf_centre[t], source ovf_src[t]) processed by the OVF variants.
 #include "launchers.hpp"
+#include "edge_v2.hpp"
 #include <cstdlib>
 
 namespace gn {
@@ -797,46 +798,6 @@ long long edge_dw2_splits(long long rows) {
         default: { constexpr int S = 32; CALL; } break; \
     }
 
-hipError_t launch_edge_fwd_v2(const EdgeGraph& g, const void* PQ, int H1p, int H1, const void* W2p, const float* b2, int H2,
-                              void* out, long long ldo, float* coords, const CoordCols& cc, unsigned char* maskB,
-                              int num_cus, hipStream_t st);
-hipError_t launch_edge_dw2_v2(const EdgeGraph& g, const void* PQ, int H1p, int H1, int H2, const void* gout,
-                              long long ldg, const unsigned char* maskB, unsigned char* hbits, float* slab,
-                              float* db2_part, int num_cus, hipStream_t st);
-hipError_t launch_edge_bwd_v2(const EdgeGraph& g, int H1p, int H2, const void* gout, long long ldg,
-                              const unsigned char* maskB, const unsigned char* hbits, const void* W2Tp, int H2p,
-                              void* dpre, void* dP, long long ldp, int num_cus, hipStream_t st, const BwdCompact* cp = nullptr);
-bool edge_bwd_v2_compact_ok(int K, int H1p, int H1);
-long long dpre_compact_tiles(int N, int K);
-hipError_t launch_dpre_plan(int N, int K, int H1p, int H1, const unsigned char* hbits, unsigned short* rowoff, int* tilesize16,
-                            int* tilebase, int* tmp, hipStream_t st);
-hipError_t launch_dq_gather_cp(int N, int K, int H1p, int H1, const unsigned char* dpre_c, const int* tilebase,
-                               const unsigned short* rowoff, const unsigned char* hbits, const void* dense_ovf_rows,
-                               const int* rev_ptr, const int* rev_rows, const int* hubs, const int* nhubs, void* dQ, long long ldq,
-                               hipStream_t st);
-bool edge_v2_shape_ok(int K, int H1p, int H2);
-bool edge_v2_max_shape_ok(int K, int H1p, int H2);
-int edge_dw2_v2_parts(int N, int K, int H1p, int num_cus);
-hipError_t launch_edge_max_fwd_v2(const EdgeGraph& g, const void* PQ, int H1p, const void* W2p, const float* b2, int H2,
-                                  void* out, long long ldo, unsigned char* maskB, int num_cus, hipStream_t st);
-hipError_t launch_edge_max_dw2_v2(const EdgeGraph& g, const void* PQ, int H1p, int H1, int H2, const void* gout,
-                                  long long ldg, const unsigned char* maskB, unsigned char* hbits, float* slab,
-                                  float* db2_part, int num_cus, hipStream_t st);
-bool edge_v2_leaky_shape_ok(int K, int H1p, int H1, int H2);
-hipError_t launch_edge_leaky_fwd_v2(const EdgeGraph& g, const void* PQ, int H1p, int H1, const void* W2p, const float* b2,
-                                    int H2, void* out, long long ldo, float* coords, const CoordCols& cc, unsigned char* maskB,
-                                    unsigned long long* tilevalid, int num_cus, hipStream_t st);
-hipError_t launch_edge_leaky_dw2_v2(const EdgeGraph& g, const void* PQ, int H1p, int H1, int H2, const void* gout,
-                                    long long ldg, const unsigned char* maskB, unsigned char* hbits,
-                                    const unsigned long long* tilevalid, float* slab, float* db2_part, int num_cus,
-                                    hipStream_t st);
-hipError_t launch_edge_leaky_bwd_v2(const EdgeGraph& g, int H1p, int H1, int H2, const void* gout, long long ldg,
-                                    const unsigned char* maskB, const unsigned char* hbits,
-                                    const unsigned long long* tilevalid, const void* W2Tp, int H2p, void* dpre, void* dP,
-                                    long long ldp, int num_cus, hipStream_t st);
-hipError_t launch_edge_max_bwd_v2(const EdgeGraph& g, int H1p, int H2, const void* gout, long long ldg,
-                                  const unsigned char* maskB, const unsigned char* hbits, const void* W2Tp, int H2p,
-                                  void* dpre, void* dP, long long ldp, int num_cus, hipStream_t st);
 constexpr int DW2_OVF_SPLITS = 128;   // x 6 column tiles = 768 workgroups at most (only the splits that hold rows run): tie-heavy graphs have ~N overflow rows
 
 int device_cus() {
@@ -866,29 +827,44 @@ static hipError_t edge_fwd_t(const EdgeGraph& g, const void* PQ, int H1p, const 
     });
     return hipGetLastError();
 }
-static bool v2_enabled() {                       // GN_DISABLE_V2=1 forces the generic kernels (A/B tests)
+// The environment switches of the edge path (the only reader under csrc/):
+//   GN_DISABLE_V2=1          tiled kernels for everything (A/B tests flip it inside one process: read on every call)
+//   GN_OVF_GEMM=0            overflow rows stay on the tiled overflow-row kernels instead of the GEMM path (A/B)
+//   GN_DPRE_COMPACT=1        the model paths take the compact-dpre kernels.  OPT-IN: exact and bit-identical, but measured
+//                            SLOWER than the dense pair at B = 4096 (edge bwd 0.98 -> 1.56 ms per launch: the in-place
+//                            halfword scatter is a phase of its own that nothing overlaps; gather 0.75 -> 1.3 ms: two
+//                            dependent loads per row and ~50 vector + ~60 scalar instructions per row) - DESIGN.md section 7h
+//   GN_EDGE_WS=<mask>        bit 0: wave-specialised relu forward (default 7: on)
+//   GN_WS_PRODUCERS_FIRST=n  which waves of the wave-specialised forward gather (round 2: producers on the four oldest
+//                            waves -1 %; re-measured at the end of round 3, after the consumer loop had changed: producers on
+//                            the YOUNGEST waves -2.2 .. -3.4 % on the forward kernel, two alternating pairs at B = 4096 -
+//                            default 0 now)
+// All but the first are read once per process.
+EdgeSwitches edge_switches() {
+    static const EdgeSwitches once = [] {
+        EdgeSwitches s = {};
+        const char* e = getenv("GN_OVF_GEMM"); s.ovf_gemm = !(e && e[0] == '0');
+        e = getenv("GN_DPRE_COMPACT"); s.dpre_compact = e && e[0] == '1';
+        e = getenv("GN_EDGE_WS"); s.edge_ws = e ? atoi(e) : 7;
+        e = getenv("GN_WS_PRODUCERS_FIRST"); s.producers_first = e ? atoi(e) : 0;
+        return s;
+    }();
+    EdgeSwitches s = once;
     const char* e = getenv("GN_DISABLE_V2");
-    return !(e && e[0] == '1');
+    s.disable_v2 = e && e[0] == '1';
+    return s;
 }
-static bool use_v2(int mode, const EdgeGraph& g, int H1p, int H2) {
-    return mode == 1 && v2_enabled() && edge_v2_shape_ok(g.K, H1p, H2);
+// The plan of a layer (edge_plan.hpp).  Forward, dW2, its reduction and the backward call this with the same arguments, so
+// they agree on what `saved` holds; act: 0 = relu after both layers (DynEdge), 1 = leaky relu + max aggregation
+// (EdgeConvTito, models/components/layers.py:72-114), 2 = leaky relu after both layers + add (DynEdgeJINST, models/gnn/
+// dynedge_jinst.py:56-98).
+static EdgePlan plan_of(int mode, const EdgeGraph& g, int H1p, int H1, int H2, int act) {
+    return edge_plan(mode, g.K, g.N, H1p, H1, H2, act, g.ovf_cnt != nullptr, edge_switches());
 }
-// act: 0 = relu after both layers (DynEdge), 2 = leaky relu after both layers (DynEdgeJINST, models/gnn/
-// dynedge_jinst.py:56-98).  The persistent kernels take the leaky variant for the DynEdge layer shapes with H1 <= 336;
-// forward, dW2 and backward of a layer must agree on the choice (same H1 to all three).
-static bool use_v2_act(int mode, const EdgeGraph& g, int H1p, int H1, int H2, int act) {
-    return use_v2(mode, g, H1p, H2) && (act == 0 || edge_v2_leaky_shape_ok(g.K, H1p, H1, H2));
+static const unsigned long long* tilevalid_of(const EdgePlan& p, const unsigned char* sb, const SavedLayout& L) {
+    return p.variant == 2 ? reinterpret_cast<const unsigned long long*>(sb + L.off_valid) : nullptr;
 }
-// ---- overflow rows on the GEMM kernels (kernels above): GN_OVF_GEMM=0 keeps the tiled overflow-row kernels (A/B)
-static bool ovf_gemm_enabled() {
-    static const bool on = [] { const char* e = getenv("GN_OVF_GEMM"); return !(e && e[0] == '0'); }();
-    return on;
-}
-// the forward's choice (no dependence on the real hidden width: the dW2 / backward passes must find what it saved)
-static bool ovf_gemm_ok(int mode, const EdgeGraph& g, int H1p, int H2, int act) {
-    return mode == 1 && (act == 0 || act == 2) && g.ovf_cnt && ovf_gemm_enabled() && use_v2(mode, g, H1p, H2) && H2 == 256 &&
-           (long long)g.N * H1p * 2 < (1LL << 31);
-}
+// ---- overflow rows on the GEMM kernels (kernels above), EdgePlan::ovf == 2
 static int ovf_grid(long long work_items) {
     const long long b = (work_items + 255) / 256;
     return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
@@ -927,16 +903,24 @@ static hipError_t launch_ovf_bwd(const EdgeGraph& g, int H1p, int H2, const unsi
     return hipGetLastError();
 }
 int edge_leaky_supported(int mode, int K, int H1p, int H1, int H2) {
-    return mode == 1 && v2_enabled() && edge_v2_leaky_shape_ok(K, H1p, H1, H2) ? 1 : 0;
+    return edge_plan(mode, K, 0, H1p, H1, H2, 2, false, edge_switches()).persistent;
+}
+int edge_max_supported(int mode, int K, int H1p, int H2) {
+    return edge_plan(mode, K, 0, H1p, H1p, H2, 1, false, edge_switches()).supported;
 }
 
 // out is float in mode 0 and bf16 in mode 1; coords (optional, [N][8] fp32) receives the columns
 // coord_cols[0..ncoord) of the fp32 result (the next layer's k-NN coordinates).
+// act = 1 (EdgeConvTito): fused kernels for bf16 tables WITHOUT overflow rows, K <= 16, H1p = H2 = 256 only -
+// hipErrorNotSupported otherwise (all three passes): the caller then runs the unfused edge-row path (csrc/generic.hip).
 hipError_t launch_edge_fwd(int mode, const EdgeGraph& g, const void* PQ, int H1p, int H1, const void* W2p, const float* b2,
                            int H2, void* out, long long ldo, float* coords, const int* coord_cols, int ncoord,
                            void* saved, hipStream_t st, int act) {
-    if (H1p % BK || g.K > 32 || ncoord < 0 || ncoord > 8 || (act != 0 && act != 2)) return hipErrorInvalidValue;
-    const bool leaky = act == 2;
+    const EdgePlan p = plan_of(mode, g, H1p, H1, H2, act);
+    if (act < 0 || act > 2) return hipErrorInvalidValue;
+    if (!p.supported) return hipErrorNotSupported;
+    if (H1p % BK || g.K > 32 || ncoord < 0 || ncoord > 8) return hipErrorInvalidValue;
+    const bool leaky = p.variant == 2;
     CoordCols cc;
     cc.n = coords ? ncoord : 0;
     for (int d = 0; d < 8; ++d) cc.c[d] = (d < cc.n) ? coord_cols[d] : -1;
@@ -946,15 +930,13 @@ hipError_t launch_edge_fwd(int mode, const EdgeGraph& g, const void* PQ, int H1p
     unsigned int* words = reinterpret_cast<unsigned int*>(sb + L.off_words);
     if (mode == 0) return edge_fwd_t<float>(g, PQ, H1p, W2p, b2, H2, out, ldo, coords, cc, words, true, leaky, st);
     // bf16: persistent weights-stationary kernel for the table rows when the shape allows it
-    const bool v2 = use_v2_act(mode, g, H1p, H1, H2, act);
-    if (v2) {
-        hipError_t e = leaky ? launch_edge_leaky_fwd_v2(g, PQ, H1p, H1, W2p, b2, H2, out, ldo, coords, cc, sb + L.off_maskB,
-                                                        reinterpret_cast<unsigned long long*>(sb + L.off_valid), device_cus(), st)
-                             : launch_edge_fwd_v2(g, PQ, H1p, H1, W2p, b2, H2, out, ldo, coords, cc, sb + L.off_maskB, device_cus(), st);
+    if (p.persistent) {
+        hipError_t e = launch_edge_fwd_v2(p.variant, g, PQ, H1p, H1, W2p, b2, H2, out, ldo, coords, cc, sb + L.off_maskB,
+                                          const_cast<unsigned long long*>(tilevalid_of(p, sb, L)), device_cus(), st);
         if (e != hipSuccess) return e;
     }
-    if (v2 && ovf_gemm_ok(mode, g, H1p, H2, act)) return launch_ovf_fwd(g, PQ, H1p, W2p, b2, H2, out, ldo, coords, cc, sb, L, st, leaky);
-    return edge_fwd_t<__bf16>(g, PQ, H1p, W2p, b2, H2, out, ldo, coords, cc, words, !v2, leaky, st);
+    if (p.ovf == 2) return launch_ovf_fwd(g, PQ, H1p, W2p, b2, H2, out, ldo, coords, cc, sb, L, st, leaky);
+    return edge_fwd_t<__bf16>(g, PQ, H1p, W2p, b2, H2, out, ldo, coords, cc, words, !p.persistent, leaky, st);
 }
 
 template <typename T>
@@ -976,30 +958,28 @@ static hipError_t edge_bwd_t(const EdgeGraph& g, const void* PQ, int H1p, int H2
     });
     return hipGetLastError();
 }
-// gout and dP are float in mode 0 and bf16 in mode 1
+// gout and dP are float in mode 0 and bf16 in mode 1.  H1: as given to the forward with act 1 / 2 (not needed with act 0)
 hipError_t launch_edge_bwd(int mode, const EdgeGraph& g, const void* PQ, int H1p, int H2, const void* gout,
                            long long ldg, const void* saved, const void* W2Tp, int H2p, void* dpre,
                            void* dP, long long ldp, hipStream_t st, int act, int H1) {
-    if (H1p % BK || H2p % BK || g.K > 32 || (ldg & (mode ? 7 : 3)) || (ldp & (mode ? 7 : 3)) || (act != 0 && act != 2))
-        return hipErrorInvalidValue;
-    const bool leaky = act == 2;
+    const EdgePlan p = plan_of(mode, g, H1p, H1, H2, act);
+    if (act < 0 || act > 2) return hipErrorInvalidValue;
+    if (!p.supported) return hipErrorNotSupported;
+    if (H1p % BK || H2p % BK || g.K > 32 || (ldg & (mode ? 7 : 3)) || (ldp & (mode ? 7 : 3))) return hipErrorInvalidValue;
+    const bool leaky = p.variant == 2;
     const SavedLayout L = saved_layout(g.N, edge_slots(g.K), H1p, H2);
     const unsigned char* sb = reinterpret_cast<const unsigned char*>(saved);
     const unsigned int* words = reinterpret_cast<const unsigned int*>(sb + L.off_words);
     if (mode == 0) return edge_bwd_t<float>(g, PQ, H1p, H2, gout, ldg, words, W2Tp, H2p, dpre, dP, ldp, true, leaky, st);
-    const bool v2 = use_v2_act(mode, g, H1p, leaky ? H1 : H1p, H2, act);
-    if (v2) {      // needs hbits: launch_edge_dw2 of this layer must have run before
-        hipError_t e = leaky ? launch_edge_leaky_bwd_v2(g, H1p, H1, H2, gout, ldg, sb + L.off_maskB, sb + L.off_hbits,
-                                                        reinterpret_cast<const unsigned long long*>(sb + L.off_valid), W2Tp, H2p,
-                                                        dpre, dP, ldp, device_cus(), st)
-                             : launch_edge_bwd_v2(g, H1p, H2, gout, ldg, sb + L.off_maskB, sb + L.off_hbits, W2Tp, H2p, dpre, dP,
-                                                  ldp, device_cus(), st);
+    if (p.persistent) {      // needs hbits: launch_edge_dw2 of this layer must have run before; H2p == 256 or not supported
+        hipError_t e = launch_edge_bwd_v2(p.variant, g, H1p, H2, gout, ldg, sb + L.off_maskB, sb + L.off_hbits, tilevalid_of(p, sb, L),
+                                          W2Tp, H2p, dpre, dP, ldp, device_cus(), st);
         if (e != hipSuccess) return e;
     }
-    if (v2 && ovf_gemm_ok(mode, g, H1p, H2, act) && H2p == 256)
+    if (p.ovf == 2)
         return launch_ovf_bwd(g, H1p, H2, sb, L, W2Tp, H2p, reinterpret_cast<__bf16*>(dpre) + (long long)g.N * edge_slots(g.K) * H1p,
                               dP, ldp, st, leaky);
-    return edge_bwd_t<__bf16>(g, PQ, H1p, H2, gout, ldg, words, W2Tp, H2p, dpre, dP, ldp, !v2, leaky, st);
+    return edge_bwd_t<__bf16>(g, PQ, H1p, H2, gout, ldg, words, W2Tp, H2p, dpre, dP, ldp, !p.persistent, leaky, st);
 }
 
 // ---- compact dpre (csrc/dpre_compact.hip): plan workspace = [rowoff u16 tiles*64 | tilesize16 int tiles | tilebase int tiles |
@@ -1017,17 +997,10 @@ DprePlan dpre_plan_layout(int N, int K, void* base) {
     p.total = off;
     return p;
 }
-// shape envelope of the compact kernels (the explicit entry points run whenever this holds) ...
-static bool dpre_compact_shape_ok(int mode, int K, int H1p, int H1, int H2) {
-    return use_v2(mode, EdgeGraph{nullptr, nullptr, nullptr, nullptr, 1, K}, H1p, H2) && edge_bwd_v2_compact_ok(K, H1p, H1);
-}
-// ... and whether the MODEL paths (step entry, per-op backward) choose them
+// whether the MODEL paths (step entry, per-op backward) choose the compact kernels (EdgePlan::compact_model; the explicit
+// entry points run whenever the shape allows, EdgePlan::compact_shape)
 int dpre_compact_supported(int mode, int K, int H1p, int H1, int H2) {
-    // OPT-IN (GN_DPRE_COMPACT=1): exact and bit-identical, but measured SLOWER than the dense pair at B = 4096 (edge bwd
-    // 0.98 -> 1.56 ms per launch: the in-place halfword scatter is a phase of its own that nothing overlaps; gather 0.75
-    // -> 1.3 ms: two dependent loads per row and ~50 vector + ~60 scalar instructions per row) - DESIGN.md section 7h
-    static const bool on = [] { const char* e = getenv("GN_DPRE_COMPACT"); return e && e[0] == '1'; }();
-    return on && dpre_compact_shape_ok(mode, K, H1p, H1, H2) ? 1 : 0;
+    return edge_plan(mode, K, 0, H1p, H1, H2, 0, false, edge_switches()).compact_model;
 }
 long long dpre_compact_bytes(int N, int K, int H1p) { return dpre_compact_tiles(N, K) * 64 * H1p * 2 + 256; }
 hipError_t launch_dpre_plan_saved(int N, int K, int H1p, int H1, int H2, const void* saved, void* plan, hipStream_t st) {
@@ -1040,7 +1013,8 @@ hipError_t launch_dpre_plan_saved(int N, int K, int H1p, int H1, int H2, const v
 hipError_t launch_edge_bwd_cp(const EdgeGraph& g, const void* PQ, int H1p, int H1, int H2, const void* gout, long long ldg,
                               const void* saved, const void* W2Tp, int H2p, void* plan, void* dpre_c, void* dpre_ovf, void* dP,
                               long long ldp, hipStream_t st) {
-    if (!dpre_compact_shape_ok(1, g.K, H1p, H1, H2)) return hipErrorNotSupported;
+    const EdgePlan pl = plan_of(1, g, H1p, H1, H2, 0);
+    if (!pl.compact_shape) return hipErrorNotSupported;
     if (H1p % BK || H2p % BK || (ldg & 7) || (ldp & 7)) return hipErrorInvalidValue;
     const int S_ = edge_slots(g.K);
     const SavedLayout L = saved_layout(g.N, S_, H1p, H2);
@@ -1049,10 +1023,10 @@ hipError_t launch_edge_bwd_cp(const EdgeGraph& g, const void* PQ, int H1p, int H
     BwdCompact cp;
     cp.rowoff = p.rowoff; cp.tilebase = p.tilebase; cp.tilesize16 = p.tilesize16;
     cp.dpre_c = reinterpret_cast<unsigned char*>(dpre_c); cp.creal = (H1 + 7) / 8;
-    hipError_t e = launch_edge_bwd_v2(g, H1p, H2, gout, ldg, sb + L.off_maskB, sb + L.off_hbits, W2Tp, H2p, nullptr, dP, ldp,
-                                      device_cus(), st, &cp);
+    hipError_t e = launch_edge_bwd_v2(0, g, H1p, H2, gout, ldg, sb + L.off_maskB, sb + L.off_hbits, nullptr, W2Tp, H2p, nullptr, dP,
+                                      ldp, device_cus(), st, &cp);
     if (e != hipSuccess) return e;
-    if (dpre_ovf && ovf_gemm_ok(1, g, H1p, H2, 0) && H2p == 256)        // same overflow-row path as the dense pair
+    if (dpre_ovf && pl.ovf == 2)                                        // same overflow-row path as the dense pair
         return launch_ovf_bwd(g, H1p, H2, sb, L, W2Tp, H2p, reinterpret_cast<__bf16*>(dpre_ovf), dP, ldp, st, false);
     // the generic kernel addresses overflow row t as row N * S + t of ONE dpre array: hand it that array's virtual base
     __bf16* virt = dpre_ovf ? reinterpret_cast<__bf16*>(dpre_ovf) - (long long)g.N * S_ * H1p : nullptr;
@@ -1078,11 +1052,29 @@ static int ovf_dw2_gemm_parts(int N, int H1, int H2) {
     const int p = gemm_tn_parts(1, N, H2, &H1, 1);
     return p <= DW2_OVF_SPLITS ? p : 0;
 }
-int edge_dw2_slabs(int mode, int N, int K, int H1p, int H2) {
-    const int S_ = edge_slots(K);
-    if (mode == 1 && v2_enabled() && edge_v2_shape_ok(K, H1p, H2)) return edge_dw2_v2_parts(N, K, H1p, device_cus()) + DW2_OVF_SPLITS;
-    return (int)edge_dw2_splits((long long)N * S_ + N);
+// The slab accounting of one layer's dW2.  total: what the caller allocates (edge_dw2_slabs) - the count of the SHAPE,
+// whatever the activation or the overflow list: outside the persistent envelope of the leaky variant the tiled kernel
+// spreads the rows over all of them.  The first nmain are always written; of the next novf, as many as `rps` says
+// (launch_reduce_slabs2: 1 = plain slabs, 0 = cut from the device-side overflow count, -1 = the GEMM's parts, all written).
+struct Dw2Slabs { int total, nmain, novf, rps; };
+static Dw2Slabs dw2_slabs(const EdgePlan& p, int N, int K, int H1p, int H1, int H2, int cus) {
+    Dw2Slabs s;
+    const int parts = edge_dw2_v2_parts(N, K, H1p, cus);
+    s.total = !p.shape_persistent ? (int)edge_dw2_splits((long long)N * edge_slots(K) + N)
+                                  : parts + (p.variant == 1 ? 0 : DW2_OVF_SPLITS);       // act 1: never overflow rows
+    s.nmain = s.total; s.novf = 0; s.rps = 1;
+    if (p.persistent) {
+        const int gemm_parts = p.ovf == 2 ? ovf_dw2_gemm_parts(N, H1, H2) : 0;
+        s.nmain = parts;
+        s.novf = gemm_parts > 0 ? gemm_parts : (p.ovf ? DW2_OVF_SPLITS : 0);
+        s.rps = gemm_parts > 0 ? -1 : 0;
+    }
+    return s;
 }
+int edge_dw2_slabs(int mode, int N, int K, int H1p, int H2) {
+    return dw2_slabs(edge_plan(mode, K, N, H1p, H1p, H2, 0, false, edge_switches()), N, K, H1p, H1p, H2, device_cus()).total;
+}
+int edge_max_dw2_slabs(int N, int K, int H1p) { return edge_dw2_v2_parts(N, K, H1p, device_cus()); }   // act 1: no overflow rows
 
 static long long dw2_rows_per_split(long long rows, int splits) {
     const long long rps = (rows + splits - 1) / splits;
@@ -1103,89 +1095,46 @@ static hipError_t edge_dw2_t(const EdgeGraph& g, const void* PQ, int H1p, int H1
 }
 hipError_t launch_edge_dw2(int mode, const EdgeGraph& g, const void* PQ, int H1p, int H1, int H2, const void* gout,
                            long long ldg, void* saved, float* slab, float* db2_part, hipStream_t st, int act) {
-    if (g.N == 0 || (ldg & (mode ? 7 : 3)) || (act != 0 && act != 2)) return hipErrorInvalidValue;
-    const bool leaky = act == 2;
+    const EdgePlan p = plan_of(mode, g, H1p, H1, H2, act);
+    if (act < 0 || act > 2) return hipErrorInvalidValue;
+    if (!p.supported) return hipErrorNotSupported;
+    if (g.N == 0 || (ldg & (mode ? 7 : 3))) return hipErrorInvalidValue;
+    const Dw2Slabs s = dw2_slabs(p, g.N, g.K, H1p, H1, H2, device_cus());
+    const bool leaky = p.variant == 2;
     const int S_ = edge_slots(g.K);
     const SavedLayout L = saved_layout(g.N, S_, H1p, H2);
     unsigned char* sb = reinterpret_cast<unsigned char*>(saved);
     const unsigned int* words = reinterpret_cast<const unsigned int*>(sb + L.off_words);
     const long long main_rows = (long long)g.N * S_;
-    if (mode == 0)
-        return edge_dw2_t<float>(g, PQ, H1p, H1, H2, gout, ldg, words, 0, main_rows + g.N, slab, db2_part,
-                                 edge_dw2_slabs(mode, g.N, g.K, H1p, H2), leaky, st);
-    // (the slab count is that of the shape, whichever kernels run: outside the persistent envelope of the leaky variant
-    // the generic kernel spreads the rows over all of them)
-    if (!use_v2_act(mode, g, H1p, H1, H2, act))
-        return edge_dw2_t<__bf16>(g, PQ, H1p, H1, H2, gout, ldg, words, 0, main_rows + g.N, slab, db2_part,
-                                  edge_dw2_slabs(mode, g.N, g.K, H1p, H2), leaky, st);
-    // persistent kernel for the table rows (also writes hbits), generic kernel for the overflow rows
-    const int parts = edge_dw2_v2_parts(g.N, g.K, H1p, device_cus());
-    hipError_t e = leaky ? launch_edge_leaky_dw2_v2(g, PQ, H1p, H1, H2, gout, ldg, sb + L.off_maskB, sb + L.off_hbits,
-                                                    reinterpret_cast<const unsigned long long*>(sb + L.off_valid), slab, db2_part,
-                                                    device_cus(), st)
-                         : launch_edge_dw2_v2(g, PQ, H1p, H1, H2, gout, ldg, sb + L.off_maskB, sb + L.off_hbits, slab, db2_part,
-                                              device_cus(), st);
+    if (mode == 0) return edge_dw2_t<float>(g, PQ, H1p, H1, H2, gout, ldg, words, 0, main_rows + g.N, slab, db2_part, s.total, leaky, st);
+    if (!p.persistent)
+        return edge_dw2_t<__bf16>(g, PQ, H1p, H1, H2, gout, ldg, words, 0, main_rows + g.N, slab, db2_part, s.total, leaky, st);
+    // persistent kernel for the table rows (also writes hbits), then the overflow rows behind its s.nmain parts
+    hipError_t e = launch_edge_dw2_v2(p.variant, g, PQ, H1p, H1, H2, gout, ldg, sb + L.off_maskB, sb + L.off_hbits,
+                                      tilevalid_of(p, sb, L), slab, db2_part, device_cus(), st);
     if (e != hipSuccess) return e;
-    // overflow rows: DW2_OVF_SPLITS row ranges over the N possible ones; a range without rows writes nothing (except the
-    // first): with a handful of overflow rows 39 of the 40 slabs were zeros written here and read back by the reduction
-    if (!g.ovf_cnt) return hipSuccess;
-    if (ovf_gemm_ok(mode, g, H1p, H2, act)) {
+    if (!p.ovf) return hipSuccess;
+    float* ovf_slab = slab + (long long)s.nmain * H2 * H1;
+    float* ovf_db2 = db2_part + (long long)s.nmain * H2;
+    if (p.ovf == 2) {
         // dm = g_out[c] (m > 0) (also the backward's operand), then - real hidden width a multiple of 8 - the partial slabs
-        // dm^T h from the transposed-operand GEMM, every one of its parts behind the main parts
+        // dm^T h from the transposed-operand GEMM
         const __bf16* h = reinterpret_cast<const __bf16*>(sb + L.off_ovf_h);
         const __bf16* m = reinterpret_cast<const __bf16*>(sb + L.off_ovf_m);
         __bf16* dm = reinterpret_cast<__bf16*>(sb + L.off_ovf_dm);
         hipLaunchKernelGGL(ovf_dm_kernel, dim3(ovf_grid((long long)g.N * (H2 / 8))), dim3(256), 0, st, g, m, H2, (const __bf16*)gout, ldg, dm,
                            leaky);
-        if (ovf_dw2_gemm_parts(g.N, H1, H2) > 0)
-            return launch_gemm_tn_parts_only(dm, H2, H2, h, H1p, H1, g.N, g.ovf_cnt, slab + (long long)parts * H2 * H1,
-                                             db2_part + (long long)parts * H2, st);
+        if (s.rps == -1) return launch_gemm_tn_parts_only(dm, H2, H2, h, H1p, H1, g.N, g.ovf_cnt, ovf_slab, ovf_db2, st);
     }
-    return edge_dw2_t<__bf16>(g, PQ, H1p, H1, H2, gout, ldg, words, main_rows, g.N,
-                              slab + (long long)parts * H2 * H1, db2_part + (long long)parts * H2, DW2_OVF_SPLITS, leaky, st, true);
+    // tiled kernel: DW2_OVF_SPLITS row ranges over the N possible ones; a range without rows writes nothing (except the
+    // first): with a handful of overflow rows 39 of the 40 slabs were zeros written here and read back by the reduction
+    return edge_dw2_t<__bf16>(g, PQ, H1p, H1, H2, gout, ldg, words, main_rows, g.N, ovf_slab, ovf_db2, DW2_OVF_SPLITS, leaky, st, true);
 }
 hipError_t launch_edge_dw2_reduce(int mode, const EdgeGraph& g, int H1p, int H1, int H2, const float* slab, const float* db2_part,
                                   float* dW2, float* db2, hipStream_t st, int act) {
     if (g.N == 0) return hipErrorInvalidValue;
-    int nmain = edge_dw2_slabs(mode, g.N, g.K, H1p, H2), novf = 0, rps = 1;
-    if (mode == 1 && use_v2_act(mode, g, H1p, H1, H2, act)) {
-        nmain = edge_dw2_v2_parts(g.N, g.K, H1p, device_cus());
-        novf = g.ovf_cnt ? DW2_OVF_SPLITS : 0;
-        rps = 0;                                           // 0: cut from the device-side count (dw2_ovf_rows_per_split)
-        if (ovf_gemm_ok(mode, g, H1p, H2, act) && ovf_dw2_gemm_parts(g.N, H1, H2) > 0) {
-            novf = ovf_dw2_gemm_parts(g.N, H1, H2);        // the GEMM's parts: all written
-            rps = -1;
-        }
-    }
-    return launch_reduce_slabs2(slab, (long long)H2 * H1, dW2, db2_part, H2, db2, nmain, novf, g.ovf_cnt, rps, st);
-}
-
-// ---- EdgeConvTito (leaky relu edge MLP, max aggregation; models/components/layers.py:72-114): fused kernels for
-// bf16 tables WITHOUT overflow rows, K <= 16, H1p = H2 = 256.  hipErrorNotSupported otherwise: the caller then runs
-// the unfused edge-row path (csrc/generic.hip).  `saved` has the layout of the relu variant (saved_layout()).
-int edge_max_supported(int mode, int K, int H1p, int H2) {
-    return mode == 1 && v2_enabled() && edge_v2_max_shape_ok(K, H1p, H2) ? 1 : 0;
-}
-int edge_max_dw2_slabs(int N, int K, int H1p) { return edge_dw2_v2_parts(N, K, H1p, device_cus()); }
-hipError_t launch_edge_max_fwd(const EdgeGraph& g, const void* PQ, int H1p, const void* W2p, const float* b2, int H2,
-                               void* out, long long ldo, void* saved, hipStream_t st) {
-    const SavedLayout L = saved_layout(g.N, edge_slots(g.K), H1p, H2);
-    return launch_edge_max_fwd_v2(g, PQ, H1p, W2p, b2, H2, out, ldo, reinterpret_cast<unsigned char*>(saved) + L.off_maskB,
-                                  device_cus(), st);
-}
-hipError_t launch_edge_max_dw2(const EdgeGraph& g, const void* PQ, int H1p, int H1, int H2, const void* gout, long long ldg,
-                               void* saved, float* slab, float* db2_part, hipStream_t st) {
-    const SavedLayout L = saved_layout(g.N, edge_slots(g.K), H1p, H2);
-    unsigned char* sb = reinterpret_cast<unsigned char*>(saved);
-    return launch_edge_max_dw2_v2(g, PQ, H1p, H1, H2, gout, ldg, sb + L.off_maskB, sb + L.off_hbits, slab, db2_part,
-                                  device_cus(), st);
-}
-hipError_t launch_edge_max_bwd(const EdgeGraph& g, int H1p, int H2, const void* gout, long long ldg, const void* saved,
-                               const void* W2Tp, int H2p, void* dpre, void* dP, long long ldp, hipStream_t st) {
-    const SavedLayout L = saved_layout(g.N, edge_slots(g.K), H1p, H2);
-    const unsigned char* sb = reinterpret_cast<const unsigned char*>(saved);
-    return launch_edge_max_bwd_v2(g, H1p, H2, gout, ldg, sb + L.off_maskB, sb + L.off_hbits, W2Tp, H2p, dpre, dP, ldp,
-                                  device_cus(), st);
+    const Dw2Slabs s = dw2_slabs(plan_of(mode, g, H1p, H1, H2, act), g.N, g.K, H1p, H1, H2, device_cus());
+    return launch_reduce_slabs2(slab, (long long)H2 * H1, dW2, db2_part, H2, db2, s.nmain, s.novf, g.ovf_cnt, s.rps, st);
 }
 
 // dQ is float in mode 0 and bf16 in mode 1 (like dpre)

@@ -19,10 +19,9 @@
 //   maskB[centre][H2]  uint8, bit s = second-relu active for slot s     (written by edge_fwd_v2)
 //   hbits[row][H1p/8]  uint8, bit c%8 of byte c/8 = h[row][c] > 0        (written by edge_dw2_v2)
 //
-// Envelope: bf16, K <= 8 (S = 8 slots), H1p in {128, 352}, H2 % 32 == 0 and <= 256 (bwd: == 256).
-// Anything else, the overflow rows, and f32 mode run the generic kernels of edgeconv.hip.
-#include "common.hpp"
-#include <cstdlib>
+// Envelope: bf16, K <= 16 (S = 8 or 16 slots), H1p in {128, 352} (256 for the max variant), H2 == 256: the shape tests are
+// in edge_plan.hpp.  Anything else, the overflow rows, and f32 mode run the generic kernels of edgeconv.hip.
+#include "edge_v2.hpp"
 
 namespace gn {
 
@@ -761,219 +760,14 @@ __host__ __device__ constexpr int stage_pitch(int row_bytes) {
     return p;
 }
 
-// The k1 (= H1p) range is split over HALVES workgroup populations so that the stationary
-// accumulator (32 x NBH*32 fp32 per wave) fits the 256-VGPR budget of 2 waves/SIMD: workgroup b
-// handles k1 blocks [kb0, kb0+nblk) (kb0 = (b % HALVES) * NBH) of the tile range b / HALVES, gathers
-// only those columns of h, and writes them into slab b / HALVES.
-template <int NB1, int NBH, int HALVES, int S, int V = 0>   // H1p = 32 * NB1, S slots per centre, V: 0 relu / 1 leaky relu
-__global__ __launch_bounds__(V2_THREADS, 2) void edge_dw2_v2_kernel(
-    EdgeGraph g, const __bf16* __restrict__ PQ, int H1, int H2,
-    const __bf16* __restrict__ gout, long long ldg, const unsigned char* __restrict__ maskB,
-    unsigned char* __restrict__ hbits, float* __restrict__ slab, float* __restrict__ db2_part, int ntiles)
-{
-    static_assert(S == 8 || S == 16, "8 or 16 slots per centre");
-    constexpr int K = NB1 * 32;
-    constexpr int CHUNKS = K / 8;
-    constexpr int NI = (NBH * 4 + 7) / 8;           // 16-byte chunks per thread (8 threads per row)
-    constexpr int HP = tr_pitch(NBH * 64);
-    constexpr int CPT = V2_ROWS / S;                // centres per tile
-    __shared__ __attribute__((aligned(16))) unsigned char Hs[2][V2_ROWS * HP];
-    __shared__ __attribute__((aligned(16))) unsigned char MaskLut[256 * 16];   // byte -> 8 x (0 / 0xFFFF) halfwords
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r = lane & 31, h = lane >> 5;
-    if (tid < 256) {
-        u32x4 e;
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj)
-            e[jj] = ((tid >> (2 * jj)) & 1 ? 0x0000ffffu : 0u) | ((tid >> (2 * jj + 1)) & 1 ? 0xffff0000u : 0u);
-        *reinterpret_cast<u32x4*>(&MaskLut[tid * 16]) = e;
-    }
-    const bool wave_on = wave * 32 < H2;
-    const int kslots = g.K;
-    const int n2 = wave * 32 + r;                   // dm column owned by this lane (A rows)
-    const int n2c = n2 < H2 ? n2 : 0;
-    const int half = (int)blockIdx.x % HALVES, part = (int)blockIdx.x / HALVES;
-    const int nparts = ((int)gridDim.x + HALVES - 1) / HALVES;
-    const int kb0 = half * NBH;
-    const int nblk = (NB1 - kb0) < NBH ? (NB1 - kb0) : NBH;       // k1 blocks of this workgroup
-    const int cbeg = kb0 * 4;
-    const int cend_all = (kb0 + nblk) * 4;                          // chunk window of this workgroup's k1 blocks ...
-    const int creal = (H1 + 7) / 8;                                 // ... of which only chunks < ceil(H1 / 8) hold real
-    const int cend = cend_all < creal ? cend_all : creal;           // columns: the zero padding is not gathered
-
-    f32x16 acc[NBH];
-#pragma unroll
-    for (int nb = 0; nb < NBH; ++nb) zero_acc(acc[nb]);
-    float bsum = 0.0f;
-
-    // ---- addressing: 32-bit offsets off the (uniform) base pointers, advanced by constants from tile to tile
-    // (no 64-bit multiplies in the loop; the launcher checks that every offset fits)
-    const int grow = tid >> 3, gc0 = tid & 7;
-    const int sl = grow % S, slc = sl < kslots ? sl : 0;
-    const bool slot_ok = sl < kslots;
-    constexpr unsigned int ROWPQ = 2u * K * 2u;                    // bytes per P|Q row
-    const unsigned char* PQb = reinterpret_cast<const unsigned char*>(PQ);
-    const unsigned char* goutb = reinterpret_cast<const unsigned char*>(gout);
-    const unsigned int ldg2 = (unsigned int)ldg * 2u;              // bytes per g_out row
-    u32x4 preg[NI], qreg[NI];
-    int cc_[NI];
-#pragma unroll
-    for (int i = 0; i < NI; ++i) { const int c = cbeg + gc0 + 8 * i; cc_[i] = c < cend ? c : cend - 1; }
-    // pad columns of this workgroup's window (chunks cend .. cend_all-1): zero once in both buffers, never written again
-    for (int idx = tid; idx < 2 * V2_ROWS * (cend_all - cend); idx += V2_THREADS) {
-        const int bufz = idx / (V2_ROWS * (cend_all - cend)), rem = idx % (V2_ROWS * (cend_all - cend));
-        const int rowz = rem / (cend_all - cend), cz = cend + rem % (cend_all - cend);
-        *reinterpret_cast<u32x4*>(&Hs[bufz][rowz * HP + (cz - cbeg) * 16]) = (u32x4){0u, 0u, 0u, 0u};
-    }
-
-    const int per = (ntiles + nparts - 1) / nparts;
-    int tile = part * per;
-    const int tile_end = min(ntiles, tile + per);
-
-// row info of tile T: centre ii, neighbour raw (loaded), validity
-#define GN_D_INFO_ISSUE(T_, ii_, raw_, ok_)                                                           \
-    {                                                                                                 \
-        const int iiu__ = (T_) * CPT + grow / S;                                                      \
-        const bool inr__ = ((T_) < ntiles) && (iiu__ < g.N);                                          \
-        (ii_) = inr__ ? iiu__ : 0;                                                                    \
-        (raw_) = g.nbr[(unsigned int)(ii_) * (unsigned int)kslots + (unsigned int)slc];               \
-        (ok_) = inr__ && slot_ok;                                                                     \
-    }
-#define GN_D_GATHER(ii_, jc_)                                                                         \
-    {                                                                                                 \
-        const unsigned int js__ = (jc_) < 0 ? 0u : (unsigned int)(jc_);                               \
-        const unsigned int po__ = __umul24((unsigned int)(ii_), ROWPQ);               \
-        const unsigned int qo__ = __umul24(js__, ROWPQ) + 2u * K;                     \
-        _Pragma("unroll") for (int i = 0; i < NI; ++i) {                                              \
-            preg[i] = *reinterpret_cast<const u32x4*>(PQb + po__ + (unsigned int)cc_[i] * 16u);       \
-            qreg[i] = *reinterpret_cast<const u32x4*>(PQb + qo__ + (unsigned int)cc_[i] * 16u);       \
-        }                                                                                             \
-    }
-// All gathered chunks are consumed (-> LDS) before the first hbits store is issued: vmcnt retires in order,
-// so a store queued between two consumed loads would make the later wait include that store's write ack.
-#define GN_D_WRITE_HT(buf_, T_)                                                                       \
-    {                                                                                                 \
-        const int rowu__ = (T_) * V2_ROWS + grow;                                                     \
-        const bool rok__ = (T_) < ntiles && rowu__ / S < g.N;                                         \
-        unsigned int hb__[NI];                                                                        \
-        _Pragma("unroll") for (int i = 0; i < NI; ++i) {                                              \
-            const u32x4 hv__ = act_sum_bf16x8<V>(preg[i], qreg[i]);                                   \
-            *reinterpret_cast<u32x4*>(&Hs[buf_][grow * HP + (cc_[i] - cbeg) * 16]) = hv__;            \
-            hb__[i] = V == 0 ? nonzero_bits_bf16x8(hv__) : positive_bits_bf16x8(hv__);                \
-        }                                                                                             \
-        if (rok__) {                                                                                  \
-            const unsigned int ho__ = (unsigned int)rowu__ * (unsigned int)CHUNKS;                    \
-            _Pragma("unroll") for (int i = 0; i < NI; ++i) hbits[ho__ + (unsigned int)cc_[i]] = (unsigned char)hb__[i]; \
-        }                                                                                             \
-    }
-    // A-side operands of one tile: k-step s covers 16 edge rows, lane half h their rows 8h..8h+7 = eight
-    // slots of ONE centre: centre 8*tile + 2s + h (S = 8) or centre 4*tile + s, slots 8h.. (S = 16).
-    // The lane needs g_out and those 8 slot bits at column n2; the four bytes are packed into one register
-#define GN_D_LOAD_A(T_, gv_, mv_)                                                                     \
-    {                                                                                                 \
-        (mv_) = 0u;                                                                                   \
-        _Pragma("unroll") for (int s = 3; s >= 0; --s) {                                              \
-            const int c__ = (S == 8) ? (T_) * 8 + 2 * s + h : (T_) * 4 + s;                           \
-            const bool ok__ = (T_) < ntiles && c__ < g.N && n2 < H2;                                  \
-            const unsigned int cs__ = ok__ ? (unsigned int)c__ : 0u;                                  \
-            const float gl__ = (float)*reinterpret_cast<const __bf16*>(goutb + cs__ * ldg2 + (unsigned int)n2c * 2u); \
-            const unsigned int mo__ = cs__ * (unsigned int)H2 + (unsigned int)n2c;                    \
-            const unsigned int ml__ = (S == 8) ? (unsigned int)maskB[mo__] : (unsigned int)maskB[mo__ * 2u + (unsigned int)h]; \
-            gv_[s] = ok__ ? gl__ : 0.0f;                                                              \
-            (mv_) = ((mv_) << 8) | (ok__ ? ml__ : 0u);                                                \
-        }                                                                                             \
-    }
-
-    int ii_n, jc_n;
-    float ga[4], gb[4];
-    unsigned int ma, mb;
-    {
-        int ii, raw; bool ok;
-        GN_D_INFO_ISSUE(tile, ii, raw, ok);
-        const int jc = ok ? raw : -1;
-        GN_D_GATHER(ii, jc);
-        GN_D_INFO_ISSUE(tile + 1, ii_n, raw, ok);
-        jc_n = ok ? raw : -1;
-        GN_D_LOAD_A(tile, ga, ma);
-        GN_D_WRITE_HT(0, tile);
-    }
-    __syncthreads();
-
-    // per-lane base of the transposed reads (k-step 0, k1 block 0, first 4-row half)
-    const int g4 = lane >> 4, li = lane & 15;
-    const int tr_base = (8 * (g4 >> 1) + (li >> 2)) * HP + (16 * (g4 & 1) + 4 * (li & 3)) * 2;
-
-    int buf = 0;
-    for (; tile < tile_end; ++tile, buf ^= 1) {
-        int ii_nn, raw_nn;
-        bool ok_nn;
-        GN_D_INFO_ISSUE(tile + 2, ii_nn, raw_nn, ok_nn);
-        GN_D_LOAD_A(tile + 1, gb, mb);
-        GN_D_GATHER(ii_n, jc_n);
-
-        if (wave_on) {
-            const unsigned char* hb = &Hs[buf][tr_base];
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                // dm^T fragment: 8 k (= the 8 slots of one centre) of column n2
-                const unsigned int gbf = pack_bf16x2(ga[s], ga[s]);
-                const unsigned int m = (ma >> (8 * s)) & 0xffu;
-                bsum += ga[s] * (float)__builtin_popcount(m);
-                // 8 slot bits -> 8 bf16 lane masks: one 16-byte LDS lookup instead of 16 bit-field extracts
-                const u32x4 mk = *reinterpret_cast<const u32x4*>(&MaskLut[m * 16]);
-                const u32x4 gb4 = {gbf, gbf, gbf, gbf};
-                const u32x4 aw = gb4 & mk;
-                const bf16x8 afrag = __builtin_bit_cast(bf16x8, aw);
-#pragma unroll
-                for (int nb = 0; nb < NBH; ++nb) {
-                    if (nb < nblk) {                                   // workgroup-uniform
-                        typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-                        const unsigned char* p0 = hb + (16 * s) * HP + nb * 64;
-                        const s16x4 t0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p0));
-                        const s16x4 t1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p0 + 4 * HP));
-                        const s16x8 bb = __builtin_shufflevector(t0, t1, 0, 1, 2, 3, 4, 5, 6, 7);
-                        acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afrag, __builtin_bit_cast(bf16x8, bb), acc[nb], 0, 0, 0);
-                    }
-                }
-            }
-        }
-
-        GN_D_WRITE_HT(buf ^ 1, tile + 1);
-        ii_n = ii_nn; jc_n = ok_nn ? raw_nn : -1;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) ga[s] = gb[s];
-        ma = mb;
-        __syncthreads();
-    }
-#undef GN_D_INFO_ISSUE
-#undef GN_D_GATHER
-#undef GN_D_WRITE_HT
-#undef GN_D_LOAD_A
-
-    // ---- write this workgroup's part of slab `part`: dW2[H2][k1 window] and (half 0) db2[H2]
-    if (wave_on) {
-        float* outp = slab + (long long)part * H2 * H1;
-#pragma unroll
-        for (int nb = 0; nb < NBH; ++nb) {
-            const int k1 = (kb0 + nb) * 32 + r;
-            if (nb < nblk && k1 < H1) {
-#pragma unroll
-                for (int q = 0; q < 16; ++q) {
-                    const int row = wave * 32 + acc_row(q, h);
-                    if (row < H2) outp[(long long)row * H1 + k1] = acc[nb][q];
-                }
-            }
-        }
-        bsum += __shfl_xor(bsum, 32);
-        if (half == 0 && h == 0 && n2 < H2) db2_part[(long long)part * H2 + n2] = bsum;
-    }
-}
-
 // =============================================================================== dW2 / db2 / hbits, software-pipelined
-// Same contraction and outputs as edge_dw2_v2_kernel; what changes is WHEN things are issued and how many waves share a
-// SIMD.  In the kernel above the two waves of a SIMD meet at the tile barrier and then run the same program: both issue
-// their MFMAs (with a wait on LDS at every k-step), then both run ~150 vector instructions with the matrix pipe idle
+// dW2[H2][H1] = dm^T h over the table's edge rows, written as partial slabs (one per tile range) with db2 = column sums of
+// dm, and the h > 0 bits the backward kernel reads.  The k1 (= H1p) range is split over HALVES workgroup populations so
+// that the stationary accumulator (32 x NBH*32 fp32 per wave) fits the 256-VGPR budget of 2 waves/SIMD: workgroup b
+// handles k1 blocks [kb0, kb0+nblk) (kb0 = (b % HALVES) * NBH) of the tile range b / HALVES, gathers only those columns
+// of h, and writes them into slab b / HALVES.
+// The kernel this one replaced was barrier-phased: the two waves of a SIMD met at the tile barrier and then ran the same
+// program, first their MFMAs (with a wait on LDS at every k-step), then ~150 vector instructions with the matrix pipe idle
 // (s_memtime probe: 3.4k cycles per tile against 1.5k of MFMA and 1.5k of vector issue per SIMD - they do not overlap
 // ACROSS waves: an MFMA that waits for the pipe holds the SIMD's vector issue, so only a wave's OWN vector instructions
 // ride in the shadow of its MFMAs).  Here every iteration is ONE straight-line block:
@@ -983,13 +777,13 @@ __global__ __launch_bounds__(V2_THREADS, 2) void edge_dw2_v2_kernel(
 //       - builds the dm^T fragments of tile T+1 from g_out / slot bytes loaded during iteration T-1, loads those of T+2,
 //       - reads the h^T fragment of a later MFMA while the current one runs (rolling window, counted waits);
 //   * NW = 4 waves (ONE per SIMD, 512 registers): a wave owns NA = 2 column blocks of dm, so an h^T fragment read from
-//     LDS feeds two MFMAs and the wave has 2 x NBLK independent accumulators; NW = 8: the blocking of the kernel above;
+//     LDS feeds two MFMAs and the wave has 2 x NBLK independent accumulators; NW = 8 (what runs): two waves per SIMD, one column block each;
 //   * no branch in the loop: look-ahead tiles past the end are clamped (loads) or land in slack rows (hbits stores,
 //     saved_layout() keeps two tiles of slack), invalid centres of the last tile are cut by one byte mask per tile;
 //   * the k1 block count of the workgroup is a template parameter (the half is chosen once, at kernel entry);
 //   * db2 = column sums of dm: when the h tile has a whole 8-column pad chunk (ceil(H1/8)*8 < H1p) its first column is
 //     set to 1.0 once and the MFMAs deliver db2 as that column of dW2 (BSUM = false); otherwise 3 instructions per
-//     k-step as before (BSUM = true).
+//     k-step on the vector ALU (BSUM = true).
 // What did NOT help (B = 4096, ms per launch, this kernel 1.25): sched_group_barrier patterns "1 MFMA, 2 LDS reads, n
 // vector instructions" (1.5-2.3: the pass also displaces the look-ahead loads), fenced matrix / vector sections with the
 // SIMD partners in opposite phases (1.34), one scheduling region per k-step (1.25), s_setprio 1 for waves 4-7 (1.25),
@@ -1684,65 +1478,60 @@ __global__ __launch_bounds__((NB1 > 8 ? NB1 : 8) * 64) void edge_bwd_v2_kernel(
 #undef GN_V2_INFO
 #undef GN_V2_GATHER_WIN
 
-// =============================================================================== launchers
-// hipErrorNotSupported = shape outside the v2 envelope (caller falls back to the generic kernels)
-int edge_slots(int K);
+// =============================================================================== launchers (prototypes: edge_v2.hpp)
+// One per pass; `variant` (EdgePlan::variant) selects the template argument V.  Each switch below lists every
+// instantiation of its kernel that exists.  hipErrorNotSupported = outside the envelope of the variant (edge_plan.hpp).
 static inline int v2_tiles(const EdgeGraph& g) { return (int)(((long long)g.N * edge_slots(g.K) + V2_ROWS - 1) / V2_ROWS); }
-// wave-specialised variants: GN_EDGE_WS is a bit mask (1 = fwd), default on
-static bool ws_enabled(int which) {
-    static int mask = -1;
-    if (mask < 0) {
-        const char* e = getenv("GN_EDGE_WS");
-        mask = e ? atoi(e) : 7;
+static bool v2_envelope(int variant, const EdgeGraph& g, int H1p, int H1, int H2) {
+    switch (variant) {
+        case 0: return edge_v2_shape_ok(g.K, H1p, H2);
+        case 1: return edge_v2_max_shape_ok(g.K, H1p, H2) && !g.ovf_cnt;
+        case 2: return edge_v2_leaky_shape_ok(g.K, H1p, H1, H2);
+        default: return false;
     }
-    return (mask >> which) & 1;
 }
-static int ws_producers_first() {
-    static int v = -1;
-    // (round 2: producers on the four oldest waves -1 %; re-measured at the end of round 3, after the consumer loop had changed:
-    //  producers on the YOUNGEST waves -2.2 .. -3.4 % on the forward kernel, two alternating pairs at B = 4096 - default 0 now)
-    if (v < 0) { const char* e = getenv("GN_WS_PRODUCERS_FIRST"); v = e ? atoi(e) : 0; }
-    return v;
+// The forward (wave-specialised) and dW2 kernels address P|Q, the output / g_out rows (pitch ld), the slot masks and the
+// h-bits with 32-bit offsets and keep node ids in 24 bits.  Forward: rows of `out` in elements (bf16x2 stores), P|Q rows
+// in bytes.  N * S * (H1p / 8) < 2^32 (h-bits, tilevalid) follows from the last term: S * (H1p / 8) <= 2 * H1p.
+static bool fwd_offsets_ok(const EdgeGraph& g, int H1p, int H2, long long ld) {
+    return (long long)g.N * (ld > H2 ? ld : H2) < (1LL << 31) && g.N < (1 << 24) && (long long)g.N * 4 * H1p < (1LL << 32);
 }
-bool edge_v2_shape_ok(int K, int H1p, int H2) {
-    return K <= 16 && H2 == 256 && (H1p == 128 || H1p == 352);
-}
-// EdgeConvTito variant (leaky relu, max aggregation): the DynTrans layer sizes of the reference, (256, 256)
-bool edge_v2_max_shape_ok(int K, int H1p, int H2) { return K <= 16 && H2 == 256 && H1p == 256; }
+// dW2: the same set for the pitch of g_out - its byte offsets N * ldg * 2 and N * H2 * 2 below 2^32 ARE the first term
+static bool dw2_offsets_ok(const EdgeGraph& g, int H1p, int H2, long long ldg) { return fwd_offsets_ok(g, H1p, H2, ldg); }
 
-hipError_t launch_edge_fwd_v2(const EdgeGraph& g, const void* PQ, int H1p, int H1, const void* W2p, const float* b2, int H2,
-                              void* out, long long ldo, float* coords, const CoordCols& cc, unsigned char* maskB,
-                              int num_cus, hipStream_t st) {
-    if (!edge_v2_shape_ok(g.K, H1p, H2)) return hipErrorNotSupported;
+hipError_t launch_edge_fwd_v2(int variant, const EdgeGraph& g, const void* PQ, int H1p, int H1, const void* W2p, const float* b2,
+                              int H2, void* out, long long ldo, float* coords, const CoordCols& cc, unsigned char* maskB,
+                              unsigned long long* tilevalid, int num_cus, hipStream_t st) {
+    if (!v2_envelope(variant, g, H1p, H1, H2)) return hipErrorNotSupported;
     if (g.N == 0) return hipSuccess;
+    const EdgeSwitches sw = edge_switches();
+    // hidden widths 337..352 (all 22 k-steps real) would need 4 more registers for the stationary W2 slice than
+    // 3 waves per SIMD leave (the variant spilled 24 bytes): the relu variant takes the all-waves-gather kernel for them,
+    // as it does with GN_EDGE_WS bit 0 clear or offsets beyond 32 bits; the other variants have no such kernel
+    const bool ws = fwd_offsets_ok(g, H1p, H2, ldo) && (variant != 0 || ((sw.edge_ws & 1) && (H1p == 128 || H1 <= 336)));
+    if (!ws && variant != 0) return hipErrorNotSupported;
     const int ntiles = v2_tiles(g);
     const int grid = ntiles < num_cus ? ntiles : num_cus;
+    const bool s8 = edge_slots(g.K) == 8;
 #define GN_FWD_LAUNCH(KS, SS)                                                                              \
     hipLaunchKernelGGL((edge_fwd_v2_kernel<KS, SS>), dim3(grid), dim3(V2_THREADS), 0, st, g, (const __bf16*)PQ,  \
                        (const __bf16*)W2p, b2, H2, (__bf16*)out, ldo, coords, cc, maskB, ntiles)
-#define GN_FWD_LAUNCH_WS(KS, KU, SS)                                                                       \
-    hipLaunchKernelGGL((edge_fwd_ws_kernel<KS, KU, SS>), dim3(grid), dim3(WS_THREADS), 0, st, g, (const __bf16*)PQ,  \
-                       (const __bf16*)W2p, b2, H2, (__bf16*)out, ldo, coords, cc, maskB, ntiles, ws_producers_first(), \
-                       (unsigned long long*)nullptr)
-    const bool s8 = edge_slots(g.K) == 8;
-    if (ws_enabled(0) && (long long)g.N * (ldo > H2 ? ldo : H2) < (1LL << 31) && g.N < (1 << 24) &&
-        (long long)g.N * 4 * H1p < (1LL << 32)) {                                    // 32-bit offsets, 24-bit node ids
-        // hidden widths 337..352 (all 22 k-steps real) would need 4 more registers for the stationary W2 slice than
-        // 3 waves per SIMD leave (the variant spilled 24 bytes): those shapes take the all-waves-gather kernel below
-        if (H1p == 128) { if (s8) GN_FWD_LAUNCH_WS(8, 8, 8); else GN_FWD_LAUNCH_WS(8, 8, 16); return hipGetLastError(); }
-        if (H1 <= 336) { if (s8) GN_FWD_LAUNCH_WS(22, 21, 8); else GN_FWD_LAUNCH_WS(22, 21, 16); return hipGetLastError(); }
+#define GN_FWD_LAUNCH_WS(KS, KU, SS, V)                                                                    \
+    hipLaunchKernelGGL((edge_fwd_ws_kernel<KS, KU, SS, V>), dim3(grid), dim3(WS_THREADS), 0, st, g, (const __bf16*)PQ, \
+                       (const __bf16*)W2p, b2, H2, (__bf16*)out, ldo, coords, cc, maskB, ntiles, sw.producers_first, tilevalid)
+#define GN_FWD_WS(KS, KU, V) { if (s8) GN_FWD_LAUNCH_WS(KS, KU, 8, V); else GN_FWD_LAUNCH_WS(KS, KU, 16, V); }
+    if (!ws) {
+        if (H1p == 128) { if (s8) GN_FWD_LAUNCH(8, 8); else GN_FWD_LAUNCH(8, 16); }
+        else { if (s8) GN_FWD_LAUNCH(22, 8); else GN_FWD_LAUNCH(22, 16); }
+    } else switch (variant) {                    // KSTEPS, KUSE: k-steps of H1p, and those that hold real columns
+        case 0: if (H1p == 128) GN_FWD_WS(8, 8, 0) else GN_FWD_WS(22, 21, 0) break;
+        case 1: GN_FWD_WS(16, 16, 1) break;
+        default: if (H1p == 128) GN_FWD_WS(8, 8, 2) else GN_FWD_WS(22, 21, 2) break;
     }
-    if (H1p == 128) { if (s8) GN_FWD_LAUNCH(8, 8); else GN_FWD_LAUNCH(8, 16); }
-    else { if (s8) GN_FWD_LAUNCH(22, 8); else GN_FWD_LAUNCH(22, 16); }
 #undef GN_FWD_LAUNCH
 #undef GN_FWD_LAUNCH_WS
+#undef GN_FWD_WS
     return hipGetLastError();
-}
-
-// GN_DW2_PIPELINED=0 selects the barrier-phased dW2 kernel (A/B measurements); default: the software-pipelined one
-static bool dw2_pipelined() {
-    static const bool on = [] { const char* e = getenv("GN_DW2_PIPELINED"); return !(e && e[0] == '0'); }();
-    return on;
 }
 
 // number of slabs (= tile-range parts) the dW2 kernel writes for N nodes
@@ -1754,206 +1543,57 @@ int edge_dw2_v2_parts(int N, int K, int H1p, int num_cus) {
     return parts > 0 ? (int)parts : 1;
 }
 
-// slab: [parts][H2][H1], db2_part: [parts][H2] with parts = edge_dw2_v2_parts()
-hipError_t launch_edge_dw2_v2(const EdgeGraph& g, const void* PQ, int H1p, int H1, int H2, const void* gout,
-                              long long ldg, const unsigned char* maskB, unsigned char* hbits, float* slab,
-                              float* db2_part, int num_cus, hipStream_t st) {
-    if (!edge_v2_shape_ok(g.K, H1p, H2)) return hipErrorNotSupported;
+hipError_t launch_edge_dw2_v2(int variant, const EdgeGraph& g, const void* PQ, int H1p, int H1, int H2, const void* gout,
+                              long long ldg, const unsigned char* maskB, unsigned char* hbits,
+                              const unsigned long long* tilevalid, float* slab, float* db2_part, int num_cus, hipStream_t st) {
+    if (!v2_envelope(variant, g, H1p, H1, H2) || !dw2_offsets_ok(g, H1p, H2, ldg)) return hipErrorNotSupported;
     if (g.N == 0) return hipSuccess;
-    // the kernel addresses P|Q, g_out, the slot masks and hbits with 32-bit offsets (and 24-bit node ids)
-    if (g.N >= (1 << 24) || (long long)g.N * 4 * H1p >= (1LL << 32) || (long long)g.N * ldg * 2 >= (1LL << 32) ||
-        (long long)g.N * H2 * 2 >= (1LL << 32) || (long long)g.N * edge_slots(g.K) * (H1p / 8) >= (1LL << 32))
-        return hipErrorNotSupported;
     const int ntiles = v2_tiles(g);
     const int parts = edge_dw2_v2_parts(g.N, g.K, H1p, num_cus);
-#define GN_DW2_LAUNCH(A, B, C, SS, GRID)                                                                    \
-    hipLaunchKernelGGL((edge_dw2_v2_kernel<A, B, C, SS>), dim3(GRID), dim3(V2_THREADS), 0, st, g, (const __bf16*)PQ, \
-                       H1, H2, (const __bf16*)gout, ldg, maskB, hbits, slab, db2_part, ntiles)
-#define GN_DW3_LAUNCH(A, B, C, SS, BS, GRID)                                                                \
-    hipLaunchKernelGGL((edge_dw2_v3_kernel<A, B, C, SS, 0, BS>), dim3(GRID), dim3(V2_THREADS), 0, st, g,           \
-                       (const __bf16*)PQ, H1, H2, (const __bf16*)gout, ldg, maskB, hbits, slab, db2_part, ntiles, \
-                       (const unsigned long long*)nullptr)
     const bool s8 = edge_slots(g.K) == 8;
-    if (dw2_pipelined()) {
-        const bool ones = (H1 + 7) / 8 * 8 < H1p;          // a whole pad chunk: db2 comes out of the MFMAs
-        if (H1p == 128) { if (s8) GN_DW3_LAUNCH(4, 4, 1, 8, true, parts); else GN_DW3_LAUNCH(4, 4, 1, 16, true, parts); }
-        else if (ones) { if (s8) GN_DW3_LAUNCH(11, 6, 2, 8, false, parts * 2); else GN_DW3_LAUNCH(11, 6, 2, 16, false, parts * 2); }
-        else { if (s8) GN_DW3_LAUNCH(11, 6, 2, 8, true, parts * 2); else GN_DW3_LAUNCH(11, 6, 2, 16, true, parts * 2); }
-    } else {
-        if (H1p == 128) { if (s8) GN_DW2_LAUNCH(4, 4, 1, 8, parts); else GN_DW2_LAUNCH(4, 4, 1, 16, parts); }
-        else { if (s8) GN_DW2_LAUNCH(11, 6, 2, 8, parts * 2); else GN_DW2_LAUNCH(11, 6, 2, 16, parts * 2); }
+#define GN_DW2_LAUNCH(NB1, NBH, HALVES, SS, V, BSUM)                                                        \
+    hipLaunchKernelGGL((edge_dw2_v3_kernel<NB1, NBH, HALVES, SS, V, BSUM>), dim3(parts * HALVES), dim3(V2_THREADS), 0, st, g, \
+                       (const __bf16*)PQ, H1, H2, (const __bf16*)gout, ldg, maskB, hbits, slab, db2_part, ntiles, tilevalid)
+#define GN_DW2(NB1, NBH, HALVES, V, BSUM) { if (s8) GN_DW2_LAUNCH(NB1, NBH, HALVES, 8, V, BSUM); else GN_DW2_LAUNCH(NB1, NBH, HALVES, 16, V, BSUM); }
+    const bool ones = (H1 + 7) / 8 * 8 < H1p;              // a whole pad chunk: db2 comes out of the MFMAs (BSUM = false)
+    switch (variant) {
+        case 0:
+            if (H1p == 128) GN_DW2(4, 4, 1, 0, true) else if (ones) GN_DW2(11, 6, 2, 0, false) else GN_DW2(11, 6, 2, 0, true)
+            break;
+        case 1: GN_DW2(8, 4, 2, 1, true) break;            // H1 == H1p == 256: no pad chunk
+        default: if (H1p == 128) GN_DW2(4, 4, 1, 2, true) else GN_DW2(11, 6, 2, 2, false) break;   // H1 <= 336: a pad chunk
     }
 #undef GN_DW2_LAUNCH
-#undef GN_DW3_LAUNCH
+#undef GN_DW2
     return hipGetLastError();
 }
 
-// cp != nullptr: compact dpre (csrc/dpre_compact.hip); dpre is then unused by the table rows
-bool edge_bwd_v2_compact_ok(int K, int H1p, int H1) {
-    return K <= 16 && (H1p == 128 || (H1p == 352 && (H1 + 7) / 8 <= 43));
-}
-hipError_t launch_edge_bwd_v2(const EdgeGraph& g, int H1p, int H2, const void* gout, long long ldg,
-                              const unsigned char* maskB, const unsigned char* hbits, const void* W2Tp, int H2p,
-                              void* dpre, void* dP, long long ldp, int num_cus, hipStream_t st, const BwdCompact* cp) {
-    if (!edge_v2_shape_ok(g.K, H1p, H2) || H2p != 256) return hipErrorNotSupported;
+hipError_t launch_edge_bwd_v2(int variant, const EdgeGraph& g, int H1p, int H2, const void* gout, long long ldg,
+                              const unsigned char* maskB, const unsigned char* hbits, const unsigned long long* tilevalid,
+                              const void* W2Tp, int H2p, void* dpre, void* dP, long long ldp, int num_cus, hipStream_t st,
+                              const BwdCompact* cp) {
+    if (!v2_envelope(variant, g, H1p, 0, H2) || H2p != 256 || (cp && variant != 0)) return hipErrorNotSupported;
     if (g.N == 0) return hipSuccess;
     const int ntiles = v2_tiles(g);
     const int grid = ntiles < num_cus ? ntiles : num_cus;
-    BwdCompact none;
-    none.rowoff = nullptr; none.tilebase = nullptr; none.tilesize16 = nullptr; none.dpre_c = nullptr; none.creal = 0;
-#define GN_BWD_LAUNCH(NB, SS, THREADS)                                                                      \
-    hipLaunchKernelGGL((edge_bwd_v2_kernel<NB, SS>), dim3(grid), dim3(THREADS), 0, st, g, (const __bf16*)gout, ldg, \
-                       maskB, hbits, (const __bf16*)W2Tp, (__bf16*)dpre, (__bf16*)dP, ldp, ntiles, none, (const unsigned long long*)nullptr)
-#define GN_BWD_LAUNCH_CP(NB, SS, THREADS)                                                                   \
-    hipLaunchKernelGGL((edge_bwd_v2_kernel<NB, SS, 0, true>), dim3(grid), dim3(THREADS), 0, st, g, (const __bf16*)gout, ldg, \
-                       maskB, hbits, (const __bf16*)W2Tp, (__bf16*)dpre, (__bf16*)dP, ldp, ntiles, *cp, (const unsigned long long*)nullptr)
     const bool s8 = edge_slots(g.K) == 8;
-    if (cp) {
-        if (H1p == 128) { if (s8) GN_BWD_LAUNCH_CP(4, 8, 512); else GN_BWD_LAUNCH_CP(4, 16, 512); }
-        else { if (s8) GN_BWD_LAUNCH_CP(11, 8, 704); else GN_BWD_LAUNCH_CP(11, 16, 704); }
-    } else {
-        if (H1p == 128) { if (s8) GN_BWD_LAUNCH(4, 8, 512); else GN_BWD_LAUNCH(4, 16, 512); }
-        else { if (s8) GN_BWD_LAUNCH(11, 8, 704); else GN_BWD_LAUNCH(11, 16, 704); }
+    const BwdCompact bc = cp ? *cp : BwdCompact{nullptr, nullptr, nullptr, nullptr, 0};
+#define GN_BWD_LAUNCH(NB1, SS, V, CP)                                                                       \
+    hipLaunchKernelGGL((edge_bwd_v2_kernel<NB1, SS, V, CP>), dim3(grid), dim3((NB1 > 8 ? NB1 : 8) * 64), 0, st, g, \
+                       (const __bf16*)gout, ldg, maskB, hbits, (const __bf16*)W2Tp, (__bf16*)dpre, (__bf16*)dP, ldp, ntiles, bc, tilevalid)
+#define GN_BWD(NB1, V, CP) { if (s8) GN_BWD_LAUNCH(NB1, 8, V, CP); else GN_BWD_LAUNCH(NB1, 16, V, CP); }
+    switch (variant) {                           // one wave per 32-column block of dh: 512 threads, 704 for H1p = 352
+        case 0:
+            if (cp) { if (H1p == 128) GN_BWD(4, 0, true) else GN_BWD(11, 0, true) }
+            else { if (H1p == 128) GN_BWD(4, 0, false) else GN_BWD(11, 0, false) }
+            break;
+        case 1: GN_BWD(8, 1, false) break;
+        default: if (H1p == 128) GN_BWD(4, 2, false) else GN_BWD(11, 2, false) break;
     }
 #undef GN_BWD_LAUNCH
-#undef GN_BWD_LAUNCH_CP
-    return hipGetLastError();
-}
-
-
-// ---- EdgeConvTito (models/components/layers.py:72-114) on the same kernels, variant V = 1 ------------------------
-// Envelope: bf16, table without overflow rows (the caller sizes K to the largest in-degree), K <= 16, H1p = H2 = 256.
-hipError_t launch_edge_max_fwd_v2(const EdgeGraph& g, const void* PQ, int H1p, const void* W2p, const float* b2, int H2,
-                                  void* out, long long ldo, unsigned char* maskB, int num_cus, hipStream_t st) {
-    if (!edge_v2_max_shape_ok(g.K, H1p, H2) || g.ovf_cnt) return hipErrorNotSupported;
-    if (g.N == 0) return hipSuccess;
-    if ((long long)g.N * (ldo > H2 ? ldo : H2) >= (1LL << 31) || g.N >= (1 << 24) || (long long)g.N * 4 * H1p >= (1LL << 32))
-        return hipErrorNotSupported;
-    const int ntiles = v2_tiles(g);
-    const int grid = ntiles < num_cus ? ntiles : num_cus;
-    CoordCols cc;
-    cc.n = 0;
-    for (int d = 0; d < 8; ++d) cc.c[d] = -1;
-    if (edge_slots(g.K) == 8)
-        hipLaunchKernelGGL((edge_fwd_ws_kernel<16, 16, 8, 1>), dim3(grid), dim3(WS_THREADS), 0, st, g, (const __bf16*)PQ,
-                           (const __bf16*)W2p, b2, H2, (__bf16*)out, ldo, (float*)nullptr, cc, maskB, ntiles, ws_producers_first(),
-                           (unsigned long long*)nullptr);
-    else
-        hipLaunchKernelGGL((edge_fwd_ws_kernel<16, 16, 16, 1>), dim3(grid), dim3(WS_THREADS), 0, st, g, (const __bf16*)PQ,
-                           (const __bf16*)W2p, b2, H2, (__bf16*)out, ldo, (float*)nullptr, cc, maskB, ntiles, ws_producers_first(),
-                           (unsigned long long*)nullptr);
-    return hipGetLastError();
-}
-hipError_t launch_edge_max_dw2_v2(const EdgeGraph& g, const void* PQ, int H1p, int H1, int H2, const void* gout,
-                                  long long ldg, const unsigned char* maskB, unsigned char* hbits, float* slab,
-                                  float* db2_part, int num_cus, hipStream_t st) {
-    if (!edge_v2_max_shape_ok(g.K, H1p, H2) || g.ovf_cnt) return hipErrorNotSupported;
-    if (g.N == 0) return hipSuccess;
-    if (g.N >= (1 << 24) || (long long)g.N * 4 * H1p >= (1LL << 32) || (long long)g.N * ldg * 2 >= (1LL << 32) ||
-        (long long)g.N * H2 * 2 >= (1LL << 32) || (long long)g.N * edge_slots(g.K) * (H1p / 8) >= (1LL << 32))
-        return hipErrorNotSupported;
-    const int ntiles = v2_tiles(g);
-    const int parts = edge_dw2_v2_parts(g.N, g.K, H1p, num_cus);
-#define GN_DWM_LAUNCH(...)                                                                                  \
-    hipLaunchKernelGGL((__VA_ARGS__), dim3(parts * 2), dim3(V2_THREADS), 0, st, g, (const __bf16*)PQ, H1, H2,     \
-                       (const __bf16*)gout, ldg, maskB, hbits, slab, db2_part, ntiles)
-#define GN_DWM3_LAUNCH(...)                                                                                 \
-    hipLaunchKernelGGL((__VA_ARGS__), dim3(parts * 2), dim3(V2_THREADS), 0, st, g, (const __bf16*)PQ, H1, H2,     \
-                       (const __bf16*)gout, ldg, maskB, hbits, slab, db2_part, ntiles, (const unsigned long long*)nullptr)
-    const bool s8 = edge_slots(g.K) == 8;
-    if (dw2_pipelined()) {      // H1 == H1p == 256: no pad chunk, db2 from the per-k-step sums
-        if (s8) GN_DWM3_LAUNCH(edge_dw2_v3_kernel<8, 4, 2, 8, 1, true>); else GN_DWM3_LAUNCH(edge_dw2_v3_kernel<8, 4, 2, 16, 1, true>);
-    } else {
-        if (s8) GN_DWM_LAUNCH(edge_dw2_v2_kernel<8, 4, 2, 8, 1>); else GN_DWM_LAUNCH(edge_dw2_v2_kernel<8, 4, 2, 16, 1>);
-    }
-#undef GN_DWM_LAUNCH
-#undef GN_DWM3_LAUNCH
-    return hipGetLastError();
-}
-hipError_t launch_edge_max_bwd_v2(const EdgeGraph& g, int H1p, int H2, const void* gout, long long ldg,
-                                  const unsigned char* maskB, const unsigned char* hbits, const void* W2Tp, int H2p,
-                                  void* dpre, void* dP, long long ldp, int num_cus, hipStream_t st) {
-    if (!edge_v2_max_shape_ok(g.K, H1p, H2) || H2p != 256 || g.ovf_cnt) return hipErrorNotSupported;
-    if (g.N == 0) return hipSuccess;
-    const int ntiles = v2_tiles(g);
-    const int grid = ntiles < num_cus ? ntiles : num_cus;
-    BwdCompact none;
-    none.rowoff = nullptr; none.tilebase = nullptr; none.tilesize16 = nullptr; none.dpre_c = nullptr; none.creal = 0;
-    if (edge_slots(g.K) == 8)
-        hipLaunchKernelGGL((edge_bwd_v2_kernel<8, 8, 1>), dim3(grid), dim3(512), 0, st, g, (const __bf16*)gout, ldg, maskB, hbits,
-                           (const __bf16*)W2Tp, (__bf16*)dpre, (__bf16*)dP, ldp, ntiles, none, (const unsigned long long*)nullptr);
-    else
-        hipLaunchKernelGGL((edge_bwd_v2_kernel<8, 16, 1>), dim3(grid), dim3(512), 0, st, g, (const __bf16*)gout, ldg, maskB, hbits,
-                           (const __bf16*)W2Tp, (__bf16*)dpre, (__bf16*)dP, ldp, ntiles, none, (const unsigned long long*)nullptr);
-    return hipGetLastError();
-}
-
-// ---- DynEdgeJINST edge convolution (models/gnn/dynedge_jinst.py:56-98: Linear, LeakyReLU, Linear, LeakyReLU, add
-// aggregation) on the same kernels, variant V = 2 ---------------------------------------------------------------------
-// Envelope: bf16, K <= 16, the DynEdge layer shapes (H1p = 128, or 352 with H1 <= 336; H2 = 256); these kernels take the
-// table rows, the overflow rows go through the generic kernels as in the relu variant.  tilevalid: one 64-bit word per 64-row tile (bit = the row is an edge), written by the forward, read by both
-// backward kernels: with a leaky second activation a row whose slot bit is clear still carries 0.01 g_out - unless it
-// does not exist.
-bool edge_v2_leaky_shape_ok(int K, int H1p, int H1, int H2) {
-    return edge_v2_shape_ok(K, H1p, H2) && (H1p == 128 || H1 <= 336);
-}
-static bool leaky_offsets_ok(const EdgeGraph& g, int H1p, int H2, long long ld) {
-    return (long long)g.N * (ld > H2 ? ld : H2) < (1LL << 31) && g.N < (1 << 24) && (long long)g.N * 4 * H1p < (1LL << 32) &&
-           (long long)g.N * edge_slots(g.K) * (H1p / 8) < (1LL << 32);
-}
-hipError_t launch_edge_leaky_fwd_v2(const EdgeGraph& g, const void* PQ, int H1p, int H1, const void* W2p, const float* b2,
-                                    int H2, void* out, long long ldo, float* coords, const CoordCols& cc, unsigned char* maskB,
-                                    unsigned long long* tilevalid, int num_cus, hipStream_t st) {
-    if (!edge_v2_leaky_shape_ok(g.K, H1p, H1, H2) || !leaky_offsets_ok(g, H1p, H2, ldo)) return hipErrorNotSupported;
-    if (g.N == 0) return hipSuccess;
-    const int ntiles = v2_tiles(g);
-    const int grid = ntiles < num_cus ? ntiles : num_cus;
-#define GN_FWL_LAUNCH(KS, KU, SS)                                                                          \
-    hipLaunchKernelGGL((edge_fwd_ws_kernel<KS, KU, SS, 2>), dim3(grid), dim3(WS_THREADS), 0, st, g, (const __bf16*)PQ, \
-                       (const __bf16*)W2p, b2, H2, (__bf16*)out, ldo, coords, cc, maskB, ntiles, ws_producers_first(), tilevalid)
-    const bool s8 = edge_slots(g.K) == 8;
-    if (H1p == 128) { if (s8) GN_FWL_LAUNCH(8, 8, 8); else GN_FWL_LAUNCH(8, 8, 16); }
-    else { if (s8) GN_FWL_LAUNCH(22, 21, 8); else GN_FWL_LAUNCH(22, 21, 16); }
-#undef GN_FWL_LAUNCH
-    return hipGetLastError();
-}
-hipError_t launch_edge_leaky_dw2_v2(const EdgeGraph& g, const void* PQ, int H1p, int H1, int H2, const void* gout,
-                                    long long ldg, const unsigned char* maskB, unsigned char* hbits,
-                                    const unsigned long long* tilevalid, float* slab, float* db2_part, int num_cus,
-                                    hipStream_t st) {
-    if (!edge_v2_leaky_shape_ok(g.K, H1p, H1, H2) || !leaky_offsets_ok(g, H1p, H2, ldg) ||
-        (long long)g.N * ldg * 2 >= (1LL << 32))
-        return hipErrorNotSupported;
-    if (g.N == 0) return hipSuccess;
-    const int ntiles = v2_tiles(g);
-    const int parts = edge_dw2_v2_parts(g.N, g.K, H1p, num_cus);
-#define GN_DWL_LAUNCH(A, B, C, SS, BS, GRID)                                                                \
-    hipLaunchKernelGGL((edge_dw2_v3_kernel<A, B, C, SS, 2, BS>), dim3(GRID), dim3(V2_THREADS), 0, st, g,           \
-                       (const __bf16*)PQ, H1, H2, (const __bf16*)gout, ldg, maskB, hbits, slab, db2_part, ntiles, tilevalid)
-    const bool s8 = edge_slots(g.K) == 8;
-    if (H1p == 128) { if (s8) GN_DWL_LAUNCH(4, 4, 1, 8, true, parts); else GN_DWL_LAUNCH(4, 4, 1, 16, true, parts); }
-    else { if (s8) GN_DWL_LAUNCH(11, 6, 2, 8, false, parts * 2); else GN_DWL_LAUNCH(11, 6, 2, 16, false, parts * 2); }   // H1 <= 336: a pad chunk
-#undef GN_DWL_LAUNCH
-    return hipGetLastError();
-}
-hipError_t launch_edge_leaky_bwd_v2(const EdgeGraph& g, int H1p, int H1, int H2, const void* gout, long long ldg,
-                                    const unsigned char* maskB, const unsigned char* hbits,
-                                    const unsigned long long* tilevalid, const void* W2Tp, int H2p, void* dpre, void* dP,
-                                    long long ldp, int num_cus, hipStream_t st) {
-    if (!edge_v2_leaky_shape_ok(g.K, H1p, H1, H2) || H2p != 256) return hipErrorNotSupported;
-    if (g.N == 0) return hipSuccess;
-    const int ntiles = v2_tiles(g);
-    const int grid = ntiles < num_cus ? ntiles : num_cus;
-    BwdCompact none;
-    none.rowoff = nullptr; none.tilebase = nullptr; none.tilesize16 = nullptr; none.dpre_c = nullptr; none.creal = 0;
-#define GN_BWL_LAUNCH(NB, SS, THREADS)                                                                      \
-    hipLaunchKernelGGL((edge_bwd_v2_kernel<NB, SS, 2>), dim3(grid), dim3(THREADS), 0, st, g, (const __bf16*)gout, ldg, \
-                       maskB, hbits, (const __bf16*)W2Tp, (__bf16*)dpre, (__bf16*)dP, ldp, ntiles, none, tilevalid)
-    const bool s8 = edge_slots(g.K) == 8;
-    if (H1p == 128) { if (s8) GN_BWL_LAUNCH(4, 8, 512); else GN_BWL_LAUNCH(4, 16, 512); }
-    else { if (s8) GN_BWL_LAUNCH(11, 8, 704); else GN_BWL_LAUNCH(11, 16, 704); }
-#undef GN_BWL_LAUNCH
+#undef GN_BWD
     return hipGetLastError();
 }
 
 }  // namespace gn
+

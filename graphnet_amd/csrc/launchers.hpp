@@ -51,7 +51,9 @@ long long edge_dw2_splits(long long rows);
 hipError_t launch_edge_fwd(int mode, const EdgeGraph& g, const void* PQ, int H1p, int H1, const void* W2p, const float* b2,
                            int H2, void* out, long long ldo, float* coords, const int* coord_cols, int ncoord,
                            void* saved, hipStream_t st, int act = 0);
-// act: 0 = relu, 2 = leaky relu after both layers (DynEdgeJINST); H1 (real hidden width) is needed with act = 2
+// act (all passes of a layer take the same, see edge_plan.hpp): 0 = relu, 1 = leaky relu + max aggregation (EdgeConvTito:
+// fused kernels or hipErrorNotSupported, edge_max_supported()), 2 = leaky relu after both layers (DynEdgeJINST);
+// H1 (real hidden width) is needed with act = 2
 hipError_t launch_edge_bwd(int mode, const EdgeGraph& g, const void* PQ, int H1p, int H2, const void* gout,
                            long long ldg, const void* saved, const void* W2Tp, int H2p, void* dpre,
                            void* dP, long long ldp, hipStream_t st, int act = 0, int H1 = 0);
@@ -64,12 +66,6 @@ hipError_t launch_edge_dw2_reduce(int mode, const EdgeGraph& g, int H1p, int H1,
                                   float* dW2, float* db2, hipStream_t st, int act = 0);
 int edge_max_supported(int mode, int K, int H1p, int H2);
 int edge_max_dw2_slabs(int N, int K, int H1p);
-hipError_t launch_edge_max_fwd(const EdgeGraph& g, const void* PQ, int H1p, const void* W2p, const float* b2, int H2,
-                               void* out, long long ldo, void* saved, hipStream_t st);
-hipError_t launch_edge_max_dw2(const EdgeGraph& g, const void* PQ, int H1p, int H1, int H2, const void* gout, long long ldg,
-                               void* saved, float* slab, float* db2_part, hipStream_t st);
-hipError_t launch_edge_max_bwd(const EdgeGraph& g, int H1p, int H2, const void* gout, long long ldg, const void* saved,
-                               const void* W2Tp, int H2p, void* dpre, void* dP, long long ldp, hipStream_t st);
 hipError_t launch_dq_gather(int mode, const void* dpre, int H1p, const int* rev_ptr, const int* rev_rows,
                             const int* hubs, const int* nhubs, int N, void* dQ, long long ldq, hipStream_t st);
 // compact dpre (dpre_compact.hip + edgeconv.hip): plan workspace of dpre_plan_layout(N, K, nullptr).total bytes

@@ -20,7 +20,6 @@
 
 namespace gn {
 int device_cus();
-int edge_dw2_slabs(int mode, int N, int K, int H1p, int H2);
 
 // ---- operand copies described by kernel ARGUMENTS (no descriptor table in device memory to keep in sync) -----------
 // dst[r * d_pitch + c] = src[r * s_row + c * s_col] - (src2 ? src2[same] : 0), r < rows, c < cols; dst fp32 or bf16
