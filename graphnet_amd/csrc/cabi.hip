@@ -66,6 +66,19 @@ int gn_knn_graph_ws(const float* x, int64_t ldx, const int32_t* cols_host, int32
     for (int d = 0; d < D; ++d) if (cols_host[d] < 0 || cols_host[d] >= ldx) return bad("gn_knn_graph_ws", "column out of range");
     return fail(gn::launch_knn(x, ldx, cols_host, D, ptr, tile_ptr, B, N, k, strict, nbr, ovf, ws, S(stream)), "gn_knn_graph_ws");
 }
+int gn_minkowski_knn_graph(const float* x, int64_t ldx, const int32_t* space_cols_host, int32_t DS, int32_t time_col,
+                           float c, float time_like_weight, const int32_t* ptr, const int32_t* tile_ptr,
+                           int32_t B, int32_t N, int32_t k, int32_t* nbr, void* stream) {
+    const char* me = "gn_minkowski_knn_graph";
+    if (N < 0 || B < 0 || k < 1 || k > 32 || DS < 1 || DS > 7) return bad(me, "need 1<=k<=32, 1<=DS<=7");
+    if (time_col < 0 || time_col >= ldx) return bad(me, "time column out of range");
+    if (!space_cols_host) return bad(me, "need space_cols_host[DS]");
+    for (int d = 0; d < DS; ++d) if (space_cols_host[d] < 0 || space_cols_host[d] >= ldx) return bad(me, "space column out of range");
+    if (N > 0 && B > 0 && !tile_ptr) return bad(me, "needs the tile plan of gn_knn_plan");
+    if (N > 0 && B > 0 && (!x || !ptr || !nbr)) return bad(me, "need x, ptr[B+1] and nbr[N, k]");
+    return fail(gn::launch_minkowski_knn(x, ldx, space_cols_host, DS, time_col, c, time_like_weight, ptr, tile_ptr, B, N, k,
+                                         nbr, S(stream)), me);
+}
 
 int64_t gn_scan_tmp_ints(int64_t n) { return (n + 2047) / 2048 + 1; }
 int gn_scan_i32(const int32_t* in, int32_t* out, int32_t n, int32_t* tmp, int32_t* total, void* stream) {

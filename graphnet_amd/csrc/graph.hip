@@ -4,6 +4,8 @@
 //                       one query per lane with a register-resident sorted (d2, j) list.
 //                       Replaces torch_cluster.knn behind torch_geometric.nn.knn_graph at
 //                       models/graphs/edges/edges.py:74-78 and models/components/layers.py:63-67.
+//                       With the Minkowski metric (template parameter MT = 1): MinkowskiKNNEdges,
+//                       models/graphs/edges/minkowski.py:66-99.
 //   ovf_*               deterministic compaction of the (k+1)-th "overflow" neighbours.
 //   rev_*               reverse adjacency (who gathers from node j) for the backward scatter.
 //   globals_kernel      homophily x4 + per-event feature means + log10(n_pulses)
@@ -21,6 +23,14 @@ constexpr int KNN_CH = 256;    // candidates per LDS chunk (8 KB: 20 single-wave
 constexpr int KNN_TILE = 64;   // queries per workgroup = one wave
 
 struct KnnCols { int c[KNN_DMAX]; };
+// Metric of the exhaustive scan (compile time).  0 = squared Euclidean distance (torch_cluster.knn).  1 = the Minkowski
+// interval of models/graphs/edges/minkowski.py:10-34,87 with the time-like branch folded in:
+//   sp = ((0 + d0*d0) + d1*d1) + ...  over the space columns;  tc = (t_i - t_j) * c;  m = sp - tc*tc;
+//   if (m < 0) m = m * (-time_like_weight)
+// fp32, operation by operation as oracle/knn_oracle.c:105-146 (no FMA contraction).  The kernel arguments of a metric
+// travel in KnnMetric<MT>: nothing for metric 0, whose kernels keep their signature's meaning and their code.
+template <int MT> struct KnnMetric {};
+template <> struct KnnMetric<1> { int tcol; float c; float ntlw; };      // time column, c, -time_like_weight
 
 // Query tiles are aligned to events: tile t of event e holds queries ptr[e]+64t .. ptr[e]+64t+63, so a
 // wave only ever scans candidates of ITS OWN event (a tile spanning events would scan their union).
@@ -94,19 +104,26 @@ __global__ __launch_bounds__(256) void knn_plan_kernel(const int* __restrict__ p
 
 // DT: number of coordinates at compile time (3 = the usual x,y,z: the distance is 8 instructions), or 0 =
 // run-time D <= 8 (every dimension guarded by a select).
+// MT: metric (KnnMetric).  MT = 1 stages the time column as one more LDS row (row DM; DT = 0 then holds up to 7 space
+// columns), keeps k-entry lists that start at (3.0e38f, -1) - raw times in ns times c reach the Euclidean 1e10f - and drops
+// the query BY INDEX where candidates are appended to the FIFO: light-like pairs and coincident pulses sit at m == 0 with
+// it, so the "k+1 list with self dropped" argument of metric 0 is not relied on.  A NaN m, or m >= 3.0e38f, never enters.
+// Events of ANY size take this exhaustive scan under MT = 1 (both launch shapes, CW = 1 and the 8-wave split): the sorted
+// sweep below is not used, its bounding-box bound is a Euclidean lower bound and proves nothing under an indefinite metric.
 // CW: waves per query tile.  CW = 1 handles the events with <= KNN_BIG pulses (one wave scans the whole
 // event).  CW = 8 handles the larger ones: the candidate range is cut in 8 contiguous pieces, one per wave,
 // each wave keeps its own sorted list, and wave 0 merges the 8 lists in ascending piece order with the same
 // insertion rule - the result is the same total order (d2, j) as one long scan.  Without it a single
 // 5000-pulse event in a batch is a 0.5 ms tail on a 0.13 ms kernel.
-template <int KMAX, int DT, int CW>
+template <int KMAX, int DT, int CW, int MT>
 __device__ __forceinline__ void knn_tile(
     const int w, unsigned char* lds_raw, unsigned char* lds_queue, const float* __restrict__ x, long long ldx, const KnnCols& cols, int Drt,
     const int* __restrict__ ptr, const int* __restrict__ tile_ptr, int B, int N, int k, int strict, int sweep_min,
-    int* __restrict__ nbr, int* __restrict__ ovf)
+    int* __restrict__ nbr, int* __restrict__ ovf, const KnnMetric<MT>& mk)
 {
 #pragma clang fp contract(off)
-    constexpr int DM = DT > 0 ? DT : KNN_DMAX;         // dimensions touched by the unrolled loops
+    constexpr int DM = DT > 0 ? DT : KNN_DMAX - MT;    // (space) dimensions touched by the unrolled loops
+    constexpr int DR = DM + MT;                        // staged rows: the time column is row DM
     const int D = DT > 0 ? DT : Drt;
     int elo = 0, ehi = B;                       // largest e with tile_ptr[e] <= w  (empty events share a value)
     while (ehi - elo > 1) {
@@ -116,25 +133,27 @@ __device__ __forceinline__ void knn_tile(
     const int ev = elo;
     const int hi = min(ptr[ev + 1], N), lo = min(max(ptr[ev], 0), hi);   // never index past x[N]
     const bool split_big = tile_ptr[B + 1] < KNN_SPLIT_MAX_TILES;         // batch-uniform (see KNN_SPLIT_MAX_TILES)
+    if constexpr (MT == 0)
     if (knn_sweep_owns(hi - lo, sweep_min)) return;                // knn_sweep_kernel owns this event
     if ((CW == 1) != (!split_big || hi - lo <= KNN_BIG)) return;   // the other launch owns this event (workgroup-uniform)
-    const int kk = k + 1;
+    const int kk = MT == 0 ? k + 1 : k;
     const int lane = (int)threadIdx.x & (KNN_TILE - 1), wv = (int)threadIdx.x / KNN_TILE;
     const int q = lo + (w - tile_ptr[ev]) * KNN_TILE + lane;
     const bool active = q < hi;
-    float (*cand)[KNN_CH] = reinterpret_cast<float (*)[KNN_CH]>(lds_raw + wv * DM * KNN_CH * 4);   // this wave's staging
+    float (*cand)[KNN_CH] = reinterpret_cast<float (*)[KNN_CH]>(lds_raw + wv * DR * KNN_CH * 4);   // this wave's staging
     float* qd = reinterpret_cast<float*>(lds_queue) + wv * (2 * KNN_QD * KNN_TILE);               // this wave's FIFOs
     int* qj = reinterpret_cast<int*>(qd + KNN_QD * KNN_TILE);
     int qn = 0;                                                                                   // entries of this lane
 
     // lanes without a query carry NaN coordinates: every distance is NaN, no comparison holds, nothing is queued
-    float qc[DM];
+    float qc[DR];
 #pragma unroll
     for (int d = 0; d < DM; ++d) qc[d] = d < D ? (active ? x[(long long)q * ldx + cols.c[d]] : __builtin_nanf("")) : 0.0f;
+    if constexpr (MT == 1) qc[DM] = active ? x[(long long)q * ldx + mk.tcol] : __builtin_nanf("");
     float bd[KMAX];
     int bj[KMAX];
 #pragma unroll
-    for (int e = 0; e < KMAX; ++e) { bd[e] = 1e10f; bj[e] = -1; }
+    for (int e = 0; e < KMAX; ++e) { bd[e] = MT == 0 ? 1e10f : 3.0e38f; bj[e] = -1; }
 
     // sorted insert after equal keys: new[t] = med3(old[t-1], d2, old[t]); the index follows
 #define GN_KNN_INSERT(d2_, j_)                                                                        \
@@ -169,7 +188,7 @@ __device__ __forceinline__ void knn_tile(
     // The chunk after the one being scanned is already on its way: its loads are issued (into registers) before the scan and
     // land in LDS after it - with 2.6 waves per SIMD (10^4-pulse events) nothing else hid the 40 staging round trips of a tile.
     constexpr int PF = KNN_CH / KNN_TILE;                    // candidates per lane and chunk
-    float pre[PF][DM];
+    float pre[PF][DR];
     auto prefetch = [&](int ci) {
         const int c0 = plo + ci * KNN_CH;
         const int cn = max(0, min(KNN_CH, phi - c0));
@@ -179,6 +198,7 @@ __device__ __forceinline__ void knn_tile(
             const float* row = x + (long long)(c0 + min(t, max(cn - 1, 0))) * ldx;
 #pragma unroll
             for (int d = 0; d < DM; ++d) pre[u][d] = (d < D && t < cn) ? row[cols.c[d]] : 3.0e38f;   // pad: d2 = inf, never taken
+            if constexpr (MT == 1) pre[u][DM] = t < cn ? row[mk.tcol] : 3.0e38f;     // (metric 1 drops the padding by index)
         }
     };
     if (nchunk > 0) prefetch(0);
@@ -194,6 +214,7 @@ __device__ __forceinline__ void knn_tile(
 #pragma unroll
                 for (int d = 0; d < DM; ++d)
                     if (d < D) cand[d][t] = pre[u][d];
+                if constexpr (MT == 1) cand[DM][t] = pre[u][DM];
             }
         }
         __syncthreads();
@@ -221,6 +242,23 @@ __device__ __forceinline__ void knn_tile(
                     }
                 }
             }
+            if constexpr (MT == 1) {
+                // sp -> m, still two packed pairs: subtract, three multiplies (dt*c, its square, the time-like branch),
+                // subtract, and one select per candidate.  dt = t_query - t_candidate as the oracle writes it.
+                const f32x4 v = *reinterpret_cast<const f32x4*>(&cand[DM][jl]);
+                const f32x2_k qt2 = {qc[DM], qc[DM]}, cc2 = {mk.c, mk.c}, nw2 = {mk.ntlw, mk.ntlw};
+#pragma unroll
+                for (int pr = 0; pr < 2; ++pr) {
+                    const f32x2_k c2 = {v[2 * pr], v[2 * pr + 1]};
+                    const f32x2_k dt = qt2 - c2;
+                    const f32x2_k tc = dt * cc2;
+                    const f32x2_k tt = tc * tc;
+                    const f32x2_k m = d2p[pr] - tt;
+                    const f32x2_k mw = m * nw2;
+                    d2p[pr][0] = m[0] < 0.0f ? mw[0] : m[0];
+                    d2p[pr][1] = m[1] < 0.0f ? mw[1] : m[1];
+                }
+            }
             // NaN / inf distances (and the NaN of lanes without a query) fail every "<" below.  The query itself is
             // scanned like any other candidate in BOTH modes: strict mode (self excluded, degree <= k) is the
             // k+1-with-self list with the query dropped and cut to k entries - the same k entries, because the
@@ -234,7 +272,8 @@ __device__ __forceinline__ void knn_tile(
             if (__ballot(dmin < thr) != 0ull) {
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
-                    if (d2v[u] < thr) {
+                    // metric 1: the query and the padding of the last group are dropped here, by index
+                    if (d2v[u] < thr && (MT == 0 || (c0 + jl + u != q && c0 + jl + u < phi))) {
                         qd[qn * KNN_TILE + lane] = d2v[u];
                         qj[qn * KNN_TILE + lane] = c0 + jl + u;
                         ++qn;
@@ -288,14 +327,14 @@ __device__ __forceinline__ void knn_tile(
     }
 }
 
-template <int KMAX, int DT, int CW>
+template <int KMAX, int DT, int CW, int MT = 0>
 __global__ __launch_bounds__(KNN_TILE * CW) void knn_kernel(
     const float* __restrict__ x, long long ldx, KnnCols cols, int Drt,
     const int* __restrict__ ptr, const int* __restrict__ tile_ptr, int B, int N, int k, int strict, int sweep_min,
-    int* __restrict__ nbr, int* __restrict__ ovf)
+    int* __restrict__ nbr, int* __restrict__ ovf, KnnMetric<MT> mk)
 {
-    constexpr int DM = DT > 0 ? DT : KNN_DMAX;
-    constexpr int CAND_BYTES = CW * DM * KNN_CH * 4;
+    constexpr int DR = DT > 0 ? DT + MT : KNN_DMAX;     // staged rows (metric 1: the space columns + the time column)
+    constexpr int CAND_BYTES = CW * DR * KNN_CH * 4;
     constexpr int LIST_BYTES = (CW - 1) * KMAX * KNN_TILE * 8;
     constexpr int LDS_BYTES = CAND_BYTES > LIST_BYTES ? CAND_BYTES : LIST_BYTES;
     constexpr int QUEUE_BYTES = CW * 2 * KNN_QD * KNN_TILE * 4;
@@ -304,11 +343,11 @@ __global__ __launch_bounds__(KNN_TILE * CW) void knn_kernel(
     unsigned char* lds_queue = lds_all + LDS_BYTES;
     if constexpr (CW == 1) {
         if ((int)blockIdx.x < tile_ptr[B])
-            knn_tile<KMAX, DT, CW>((int)blockIdx.x, lds_raw, lds_queue, x, ldx, cols, Drt, ptr, tile_ptr, B, N, k, strict, sweep_min, nbr, ovf);
+            knn_tile<KMAX, DT, CW, MT>((int)blockIdx.x, lds_raw, lds_queue, x, ldx, cols, Drt, ptr, tile_ptr, B, N, k, strict, sweep_min, nbr, ovf, mk);
     } else {
         const int nbig = tile_ptr[B + 1] < KNN_SPLIT_MAX_TILES ? tile_ptr[B + 1] : 0;   // usually 0: the workgroups leave at once
         for (int i = blockIdx.x; i < nbig; i += gridDim.x) {
-            knn_tile<KMAX, DT, CW>(tile_ptr[B + 2 + i], lds_raw, lds_queue, x, ldx, cols, Drt, ptr, tile_ptr, B, N, k, strict, sweep_min, nbr, ovf);
+            knn_tile<KMAX, DT, CW, MT>(tile_ptr[B + 2 + i], lds_raw, lds_queue, x, ldx, cols, Drt, ptr, tile_ptr, B, N, k, strict, sweep_min, nbr, ovf, mk);
             __syncthreads();                                 // LDS reuse by the next tile
         }
     }
@@ -1160,19 +1199,19 @@ hipError_t launch_knn(const float* x, long long ldx, const int* cols, int D, con
         const dim3 blockb(KNN_TILE * 8), gridb(1024);        /* second launch: events above KNN_BIG pulses */   \
         if (D == 3) {                                                                                           \
             hipLaunchKernelGGL((knn_kernel<KM, 3, 1>), grid, block, 0, st, x, ldx, kc, D, ptr, tile_ptr, B, N, k, \
-                               strict, smin, nbr, ovf);                                                         \
+                               strict, smin, nbr, ovf, KnnMetric<0>());                                        \
             if (bigpossible)                                                                                    \
                 hipLaunchKernelGGL((knn_kernel<KM, 3, 8>), gridb, blockb, 0, st, x, ldx, kc, D, ptr, tile_ptr, B, N, \
-                                   k, strict, smin, nbr, ovf);                                                  \
+                                   k, strict, smin, nbr, ovf, KnnMetric<0>());                                 \
             if (sweep)                                                                                          \
                 hipLaunchKernelGGL((knn_sweep_kernel<KM, 3>), grid, block, 0, st, D, ptr, tile_ptr, B, N, k, strict, \
                                    smin, L.sidx, L.sx, L.bbox, L.bminj, nbr, ovf);                              \
         } else {                                                                                                \
             hipLaunchKernelGGL((knn_kernel<KM, 0, 1>), grid, block, 0, st, x, ldx, kc, D, ptr, tile_ptr, B, N, k, \
-                               strict, smin, nbr, ovf);                                                         \
+                               strict, smin, nbr, ovf, KnnMetric<0>());                                        \
             if (bigpossible)                                                                                    \
                 hipLaunchKernelGGL((knn_kernel<KM, 0, 8>), gridb, blockb, 0, st, x, ldx, kc, D, ptr, tile_ptr, B, N, \
-                                   k, strict, smin, nbr, ovf);                                                  \
+                                   k, strict, smin, nbr, ovf, KnnMetric<0>());                                 \
             if (sweep)                                                                                          \
                 hipLaunchKernelGGL((knn_sweep_kernel<KM, 0>), grid, block, 0, st, D, ptr, tile_ptr, B, N, k, strict, \
                                    smin, L.sidx, L.sx, L.bbox, L.bminj, nbr, ovf);                              \
@@ -1183,6 +1222,42 @@ hipError_t launch_knn(const float* x, long long ldx, const int* cols, int D, con
     else if (kk <= 17) GN_KNN_LAUNCH(17)
     else GN_KNN_LAUNCH(33)
 #undef GN_KNN_LAUNCH
+    return hipGetLastError();
+}
+
+// k-NN under the Minkowski metric (KnnMetric<1>): the strict table nbr[N, k], degree min(k, n - 1), ascending (m, j).
+// Always the exhaustive scan, whatever the event sizes (see knn_tile): one launch, plus the 8-wave launch when the batch
+// can hold an event above KNN_BIG pulses.  Lists of 8 / 16 / 32 entries: k of them are written.
+hipError_t launch_minkowski_knn(const float* x, long long ldx, const int* space_cols, int DS, int time_col, float c,
+                                float time_like_weight, const int* ptr, const int* tile_ptr, int B, int N, int k, int* nbr,
+                                hipStream_t st) {
+    if (N == 0 || B == 0) return hipSuccess;
+    KnnCols kc;
+    for (int d = 0; d < KNN_DMAX; ++d) kc.c[d] = d < DS ? space_cols[d] : 0;
+    KnnMetric<1> mk;
+    mk.tcol = time_col; mk.c = c; mk.ntlw = -time_like_weight;
+    const long long tiles = (long long)N / KNN_TILE + B;
+    const dim3 grid((unsigned)tiles), block(KNN_TILE), blockb(KNN_TILE * 8), gridb(1024);
+    const bool bigpossible = N > KNN_BIG;
+    int* const no_ovf = nullptr;
+#define GN_MINK_LAUNCH(KM, DT_)                                                                                 \
+    {                                                                                                           \
+        hipLaunchKernelGGL((knn_kernel<KM, DT_, 1, 1>), grid, block, 0, st, x, ldx, kc, DS, ptr, tile_ptr, B, N, k, 1, \
+                           KNN_SWEEP_MAX, nbr, no_ovf, mk);                                                     \
+        if (bigpossible)                                                                                        \
+            hipLaunchKernelGGL((knn_kernel<KM, DT_, 8, 1>), gridb, blockb, 0, st, x, ldx, kc, DS, ptr, tile_ptr, B, N, \
+                               k, 1, KNN_SWEEP_MAX, nbr, no_ovf, mk);                                           \
+    }
+#define GN_MINK_LAUNCH_K(DT_)                                                                                   \
+    {                                                                                                           \
+        if (k <= 8) GN_MINK_LAUNCH(8, DT_)                                                                      \
+        else if (k <= 16) GN_MINK_LAUNCH(16, DT_)                                                               \
+        else GN_MINK_LAUNCH(32, DT_)                                                                            \
+    }
+    if (DS == 3) GN_MINK_LAUNCH_K(3)
+    else GN_MINK_LAUNCH_K(0)
+#undef GN_MINK_LAUNCH_K
+#undef GN_MINK_LAUNCH
     return hipGetLastError();
 }
 

@@ -17,6 +17,7 @@ import torch
 from torch import Tensor
 
 from . import ops
+from .graphs import minkowski_record
 from .model import REFERENCE, Model
 
 GLOBAL_POOLINGS = ("min", "max", "sum", "mean")
@@ -845,6 +846,12 @@ class DynEdge(GNN):
         ei = _maybe(data, "edge_index")
         if ei is not None:
             return ops.table_from_edge_index(ei, int(x.shape[0]), self._nb_neighbours)
+        mink = minkowski_record(data)
+        if mink is not None:        # recorded by MinkowskiKNNEdges on a CPU Data: one launch for the whole batch, here
+            k, c, tlw, time_coord, space_coords = mink
+            plan = ops.knn_plan(ptr32, int(x.shape[0]))
+            self.__dict__["_last_plan"] = plan
+            return ops.minkowski_knn_graph(x, space_coords, time_coord, c, tlw, batch32, ptr32, k, plan=plan)
         k, cols = self._nb_neighbours, self._graph_columns
         knn_k = _maybe(data, "knn_k")
         if knn_k is not None:       # recorded by KNNEdges on a CPU Data: same k / columns, built here
@@ -895,7 +902,7 @@ class DynEdge(GNN):
             from .step import DynEdgeStepFunction
             box: dict = {}
             if isinstance(_maybe(data, "nbr_table"), ops.NeighbourTable) or _maybe(data, "edge_index") is not None or \
-                    _maybe(data, "knn_k") is not None:
+                    _maybe(data, "knn_k") is not None or _maybe(data, "mink_k") is not None:
                 box["table"] = self._layer0_graph(data, x, batch32, ptr32)      # the caller's graph (or its k / columns)
             out = DynEdgeStepFunction.apply(stepper, box, x.contiguous(), ptr32, batch32, n_pulses, *self._kernel_params())
             if self._add_global_variables_after_pooling:

@@ -245,6 +245,32 @@ def knn_graph(x: Tensor, cols: Sequence[int], batch: Tensor, ptr: Tensor, k: int
     return table
 
 
+def minkowski_knn_graph(x: Tensor, space_cols: Sequence[int], time_col: int, c: float, time_like_weight: float,
+                        batch: Tensor, ptr: Tensor, k: int, plan: Optional[Tensor] = None) -> NeighbourTable:
+    """Batched k-NN under the Minkowski metric inside each event (``gn_minkowski_knn_graph``; the reference's
+    ``MinkowskiKNNEdges``, ``graphs/edges/minkowski.py:66-99``): ``m = |dx|^2 - (c dt)^2`` on ``x[:, space_cols]`` and
+    ``x[:, time_col]``, negative (time-like) ``m`` scaled by ``-time_like_weight``, per centre the ``k`` smallest
+    ``(m, j)`` with the centre excluded by index.  Returns the strict table (degree ``min(k, n - 1)``, no overflow
+    column).  Events of any size are scanned exhaustively: the sorted sweep's pruning bound is Euclidean."""
+    if plan is None:
+        plan = knn_plan(ptr, int(x.shape[0]))
+    _need(x, torch.float32, "x"); _need(batch, torch.int32, "batch"); _need(ptr, torch.int32, "ptr")
+    N = int(x.shape[0])
+    ld = _rows(x, "x")
+    if any(not 0 <= int(v) < int(x.shape[1]) for v in list(space_cols) + [time_col]):
+        raise ValueError(f"minkowski_knn_graph: columns {list(space_cols)} / {time_col} outside x[:, :{int(x.shape[1])}]")
+    nbr = torch.empty((N, k), dtype=torch.int32, device=x.device)
+    sc = (ctypes.c_int32 * len(space_cols))(*[int(v) for v in space_cols])
+    B = int(ptr.shape[0]) - 1
+    with _timed("minkowski_knn_graph"):
+        _lib.check(_lib.lib().gn_minkowski_knn_graph(_p(x), ld, ctypes.cast(sc, ctypes.c_void_p), len(space_cols),
+                                                     int(time_col), float(c), float(time_like_weight), _p(ptr), _p(plan),
+                                                     B, N, k, _p(nbr), _st()))
+    table = _finish_table(nbr, None, k)
+    table.event_ptr = ptr       # every edge stays inside its event: the reverse lists can be built event by event
+    return table
+
+
 def table_from_edge_index(edge_index: Tensor, N: int, K: int) -> NeighbourTable:
     """Loader-supplied ``edge_index`` -> neighbour table.  PyG's ``EdgeConv`` takes edges in any order and of any
     in-degree, so this does too: edges that are not grouped by ascending target are stable-sorted by target first,

@@ -62,6 +62,16 @@ int gn_knn_graph_ws(const float* x, int64_t ldx, const int32_t* cols_host, int32
  * tile_ptr[B+1] = number of tiles that belong to events above 1024 pulses, their ids from tile_ptr[B+2]
  * (those tiles are scanned by 8 waves each, the others by one). */
 int gn_knn_plan(const int32_t* ptr, int32_t B, int32_t* tile_ptr, void* stream);
+/* MinkowskiKNNEdges (models/graphs/edges/minkowski.py:66-99), per centre: among the pulses j != i of its own event the k
+ * smallest in the total order (m, j), fp32 without FMA contraction:
+ *   sp = ((0 + d0*d0) + d1*d1) + ... over space_cols;  tc = (t_i - t_j) * c;  m = sp - tc*tc;
+ *   if (m < 0) m = m * (-time_like_weight)
+ * The query is excluded by index; a NaN m or m >= 3.0e38f is nobody's neighbour.  nbr[N, k]: the strict table (degree
+ * min(k, n - 1), ascending (m, j), -1 padded, no overflow column).  space_cols: HOST int[DS], 1 <= DS <= 7; every column
+ * < ldx; 1 <= k <= 32; tile_ptr: the plan of gn_knn_plan.  Events of any size are scanned exhaustively. */
+int gn_minkowski_knn_graph(const float* x, int64_t ldx, const int32_t* space_cols_host, int32_t DS, int32_t time_col,
+                           float c, float time_like_weight, const int32_t* ptr, const int32_t* tile_ptr,
+                           int32_t B, int32_t N, int32_t k, int32_t* nbr, void* stream);
 
 /* exclusive scan; tmp: >= gn_scan_tmp_ints(n) ints; total (optional) receives the sum */
 int64_t gn_scan_tmp_ints(int64_t n);
