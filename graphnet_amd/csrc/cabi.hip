@@ -79,6 +79,20 @@ int gn_minkowski_knn_graph(const float* x, int64_t ldx, const int32_t* space_col
     return fail(gn::launch_minkowski_knn(x, ldx, space_cols_host, DS, time_col, c, time_like_weight, ptr, tile_ptr, B, N, k,
                                          nbr, S(stream)), me);
 }
+int64_t gn_radius_work_ints(int32_t B, int32_t N) { return (B < 0 || N < 0) ? -1 : gn::radius_work_ints(B, N); }
+int gn_radius_graph(const float* x, int64_t ldx, const int32_t* cols_host, int32_t D, float r, const int32_t* ptr,
+                    const int32_t* tile_ptr, int32_t B, int32_t N, int32_t cap, int32_t* nbr, int32_t* deg, int32_t* work,
+                    void* stream) {
+    const char* me = "gn_radius_graph";
+    if (N < 0 || B < 0 || cap < 1 || cap > 32 || D < 1 || D > 8) return bad(me, "need 1<=cap<=32, 1<=D<=8");
+    if (!(r > 0.0f) || !(r <= 3.4028234e38f)) return bad(me, "need a finite radius > 0");
+    if (!cols_host) return bad(me, "need cols_host[D]");
+    for (int d = 0; d < D; ++d) if (cols_host[d] < 0 || cols_host[d] >= ldx) return bad(me, "column out of range");
+    if (!tile_ptr) return bad(me, "needs the tile plan of gn_knn_plan");
+    if (N > 0 && B > 0 && (!x || !ptr || !nbr || !deg || !work))
+        return bad(me, "need x, ptr[B+1], nbr[N, cap], deg[N] and work[gn_radius_work_ints(B, N)]");
+    return fail(gn::launch_radius_graph(x, ldx, cols_host, D, r, ptr, tile_ptr, B, N, cap, nbr, deg, work, S(stream)), me);
+}
 
 int64_t gn_scan_tmp_ints(int64_t n) { return (n + 2047) / 2048 + 1; }
 int gn_scan_i32(const int32_t* in, int32_t* out, int32_t n, int32_t* tmp, int32_t* total, void* stream) {

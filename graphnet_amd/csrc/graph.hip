@@ -6,6 +6,8 @@
 //                       models/graphs/edges/edges.py:74-78 and models/components/layers.py:63-67.
 //                       With the Minkowski metric (template parameter MT = 1): MinkowskiKNNEdges,
 //                       models/graphs/edges/minkowski.py:66-99.
+//   radius_*_kernel     per-event radius graph with a neighbour cap (RadialEdges, models/graphs/edges/edges.py:83-117):
+//                       in-radius candidates appended in index order; centres above the cap redone with the k-NN list.
 //   ovf_*               deterministic compaction of the (k+1)-th "overflow" neighbours.
 //   rev_*               reverse adjacency (who gathers from node j) for the backward scatter.
 //   globals_kernel      homophily x4 + per-event feature means + log10(n_pulses)
@@ -306,8 +308,6 @@ __device__ __forceinline__ void knn_tile(
                 GN_KNN_INSERT(d2, j);
             }
     }
-#undef GN_KNN_INSERT
-#undef GN_KNN_FLUSH
     if (active && wv == 0) {
         int c = 0;
         int extra = -1;
@@ -352,6 +352,199 @@ __global__ __launch_bounds__(KNN_TILE * CW) void knn_kernel(
         }
     }
 }
+
+// ---------------------------------------------------------------- radius graph (RadialEdges, models/graphs/edges/edges.py:83-117)
+// Edge j -> i iff j != i, same event and d2(i, j) < r2 (strict; d2 as in knn_tile: fp32, left to right, no contraction).
+// A k-NN list pays ~4 KMAX vector instructions of sorted insert per accepted candidate and a radius graph accepts EVERY
+// in-radius candidate, so the common path keeps no list: candidates arrive in ascending index, an in-radius one is stored
+// at slot = running count of the centre's row (while the count is below cap) and counted.  A centre that ends at or
+// under the cap is finished, already ascending by j.  A tile with a centre above the cap appends its id to a list on the
+// device (work[0] = count, ids from work[1]; no host read-back) and radius_overflow_kernel redoes those centres.
+//
+// radius_scan: the exhaustive scan of one event by one wave, one query per lane - staging, prefetch and the packed-pair
+// distance of knn_tile - handing every group of four candidates (j0 .. j0 + 3, d2[4]) to f.  Padding of the last group
+// has d2 = inf or NaN and so does everything of a lane without a query (NaN coordinates): no "<" holds for them.
+template <int DT, class F>
+__device__ __forceinline__ void radius_scan(
+    float (*cand)[KNN_CH], const float* __restrict__ x, long long ldx, const KnnCols& cols, int Drt, int lo, int hi, int lane,
+    const float (&qc)[DT > 0 ? DT : KNN_DMAX], F&& f)
+{
+#pragma clang fp contract(off)
+    constexpr int DM = DT > 0 ? DT : KNN_DMAX;
+    const int D = DT > 0 ? DT : Drt;
+    const int nchunk = (hi - lo + KNN_CH - 1) / KNN_CH;
+    constexpr int PF = KNN_CH / KNN_TILE;
+    float pre[PF][DM];
+    auto prefetch = [&](int ci) {
+        const int c0 = lo + ci * KNN_CH;
+        const int cn = max(0, min(KNN_CH, hi - c0));
+#pragma unroll
+        for (int u = 0; u < PF; ++u) {
+            const int t = lane + u * KNN_TILE;
+            const float* row = x + (long long)(c0 + min(t, max(cn - 1, 0))) * ldx;
+#pragma unroll
+            for (int d = 0; d < DM; ++d) pre[u][d] = (d < D && t < cn) ? row[cols.c[d]] : 3.0e38f;   // pad: d2 = inf
+        }
+    };
+    if (nchunk > 0) prefetch(0);
+    for (int ci = 0; ci < nchunk; ++ci) {
+        const int c0 = lo + ci * KNN_CH;
+        const int cn = max(0, min(KNN_CH, hi - c0));
+        const int cn4 = (cn + 3) & ~3;
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < PF; ++u) {
+            const int t = lane + u * KNN_TILE;
+            if (t < cn4) {
+#pragma unroll
+                for (int d = 0; d < DM; ++d)
+                    if (d < D) cand[d][t] = pre[u][d];
+            }
+        }
+        __syncthreads();
+        if (ci + 1 < nchunk) prefetch(ci + 1);
+        for (int jl = 0; jl < cn4; jl += 4) {
+            typedef float f32x2_r __attribute__((ext_vector_type(2)));
+            f32x2_r d2p[2] = {{0.0f, 0.0f}, {0.0f, 0.0f}};
+#pragma unroll
+            for (int d = 0; d < DM; ++d) {
+                if (d < D) {
+                    const f32x4 v = *reinterpret_cast<const f32x4*>(&cand[d][jl]);
+                    const f32x2_r q2 = {qc[d], qc[d]};
+#pragma unroll
+                    for (int pr = 0; pr < 2; ++pr) {
+                        const f32x2_r c2 = {v[2 * pr], v[2 * pr + 1]};
+                        const f32x2_r diff = c2 - q2;
+                        const f32x2_r sq = diff * diff;
+                        d2p[pr] = d2p[pr] + sq;         // 0 + sq first: the contract's left-to-right sum
+                    }
+                }
+            }
+            const float d2v[4] = {d2p[0][0], d2p[0][1], d2p[1][0], d2p[1][1]};
+            f(c0 + jl, d2v);
+        }
+    }
+}
+
+// The event of query tile w and this lane's query: lo / hi = the event's pulse range, q = the query (q >= hi: none).
+__device__ __forceinline__ void radius_tile_of(int w, const int* __restrict__ ptr, const int* __restrict__ tile_ptr, int B, int N,
+                                               int lane, int& lo, int& hi, int& q) {
+    int elo = 0, ehi = B;                       // largest e with tile_ptr[e] <= w  (empty events share a value)
+    while (ehi - elo > 1) {
+        const int mid = (elo + ehi) >> 1;
+        if (tile_ptr[mid] <= w) elo = mid; else ehi = mid;
+    }
+    hi = min(ptr[elo + 1], N); lo = min(max(ptr[elo], 0), hi);            // never index past x[N]
+    q = lo + (w - tile_ptr[elo]) * KNN_TILE + lane;
+}
+
+// Common path: one wave per query tile, events of any size.  nbr[N, cap] (-1 padded), deg[N] = the UNCAPPED count.
+template <int DT>
+__global__ __launch_bounds__(KNN_TILE) void radius_append_kernel(
+    const float* __restrict__ x, long long ldx, KnnCols cols, int Drt, float r2,
+    const int* __restrict__ ptr, const int* __restrict__ tile_ptr, int B, int N, int cap,
+    int* __restrict__ nbr, int* __restrict__ deg, int* __restrict__ work)
+{
+    constexpr int DM = DT > 0 ? DT : KNN_DMAX;
+    const int D = DT > 0 ? DT : Drt;
+    __shared__ __attribute__((aligned(16))) float cand[DM][KNN_CH];
+    const int w = (int)blockIdx.x, lane = (int)threadIdx.x;
+    if (w >= tile_ptr[B]) return;
+    int lo, hi, q;
+    radius_tile_of(w, ptr, tile_ptr, B, N, lane, lo, hi, q);
+    const bool active = q < hi;
+    float qc[DM];
+#pragma unroll
+    for (int d = 0; d < DM; ++d) qc[d] = d < D ? (active ? x[(long long)q * ldx + cols.c[d]] : __builtin_nanf("")) : 0.0f;
+    int* const row = nbr + (long long)q * cap;              // touched by lanes with a query only
+    int cnt = 0;
+    radius_scan<DT>(cand, x, ldx, cols, Drt, lo, hi, lane, qc, [&](int j0, const float (&d2v)[4]) {
+        const float dmin = __builtin_fminf(__builtin_fminf(d2v[0], d2v[1]), __builtin_fminf(d2v[2], d2v[3]));
+        if (__ballot(dmin < r2) != 0ull) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                if (d2v[u] < r2 && j0 + u != q && active) {          // the centre is dropped by index
+                    if (cnt < cap) row[cnt] = j0 + u;
+                    ++cnt;
+                }
+            }
+        }
+    });
+    if (active) {
+        for (int c = cnt; c < cap; ++c) row[c] = -1;
+        deg[q] = cnt;
+    }
+    if (__ballot(active && cnt > cap) != 0ull && lane == 0) work[1 + atomicAdd(&work[0], 1)] = w;
+}
+
+// Rare path: the tiles listed in work, a few workgroups striding over them.  Every centre of such a tile above the cap
+// keeps a register-resident sorted (d2, j) list as knn_tile does (FIFO and insert are knn_tile's), started at (r2, -1) so
+// that only in-radius candidates enter, the centre dropped by index.  Its cap-th entry (td, tj) is the largest kept key:
+// a second scan stores every in-radius j with (d2, j) <= (td, tj) - exactly cap of them, the distances are the same bits -
+// in ascending j, which is the order the table wants and costs no sort of the list.
+template <int KMAX, int DT>
+__global__ __launch_bounds__(KNN_TILE) void radius_overflow_kernel(
+    const float* __restrict__ x, long long ldx, KnnCols cols, int Drt, float r2,
+    const int* __restrict__ ptr, const int* __restrict__ tile_ptr, int B, int N, int cap,
+    int* __restrict__ nbr, const int* __restrict__ deg, const int* __restrict__ work)
+{
+    constexpr int DM = DT > 0 ? DT : KNN_DMAX;
+    const int D = DT > 0 ? DT : Drt;
+    __shared__ __attribute__((aligned(16))) float cand[DM][KNN_CH];
+    __shared__ float qd[KNN_QD * KNN_TILE];
+    __shared__ int qj[KNN_QD * KNN_TILE];
+    const int lane = (int)threadIdx.x;
+    const int ntile = min(work[0], tile_ptr[B]);
+    for (int i = (int)blockIdx.x; i < ntile; i += (int)gridDim.x) {
+        const int w = work[1 + i];
+        int lo, hi, q;
+        radius_tile_of(w, ptr, tile_ptr, B, N, lane, lo, hi, q);
+        const bool over = q < hi && deg[q] > cap;           // the others are finished (and scan as lanes without a query)
+        float qc[DM];
+#pragma unroll
+        for (int d = 0; d < DM; ++d) qc[d] = d < D ? (over ? x[(long long)q * ldx + cols.c[d]] : __builtin_nanf("")) : 0.0f;
+        float bd[KMAX];
+        int bj[KMAX];
+#pragma unroll
+        for (int e = 0; e < KMAX; ++e) { bd[e] = r2; bj[e] = -1; }
+        int qn = 0;
+        radius_scan<DT>(cand, x, ldx, cols, Drt, lo, hi, lane, qc, [&](int j0, const float (&d2v)[4]) {
+            const float thr = bd[KMAX - 1];
+            const float dmin = __builtin_fminf(__builtin_fminf(d2v[0], d2v[1]), __builtin_fminf(d2v[2], d2v[3]));
+            if (__ballot(dmin < thr) != 0ull) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    if (d2v[u] < thr && j0 + u != q) {
+                        qd[qn * KNN_TILE + lane] = d2v[u];
+                        qj[qn * KNN_TILE + lane] = j0 + u;
+                        ++qn;
+                    }
+                }
+                if (__ballot(qn > KNN_QD - 4) != 0ull) GN_KNN_FLUSH();
+            }
+        });
+        GN_KNN_FLUSH();
+        float td = -1.0f;                                   // lanes that are not over keep nothing (d2 >= 0)
+        int tj = -1;
+#pragma unroll
+        for (int e = 0; e < KMAX; ++e)
+            if (e == cap - 1 && over) { td = bd[e]; tj = bj[e]; }
+        int* const row = nbr + (long long)q * cap;          // touched by lanes that are over only
+        int cnt = 0;
+        radius_scan<DT>(cand, x, ldx, cols, Drt, lo, hi, lane, qc, [&](int j0, const float (&d2v)[4]) {
+            const float dmin = __builtin_fminf(__builtin_fminf(d2v[0], d2v[1]), __builtin_fminf(d2v[2], d2v[3]));
+            if (__ballot(dmin <= td) != 0ull) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int j = j0 + u;
+                    if ((d2v[u] < td || (d2v[u] == td && j <= tj)) && j != q && cnt < cap) row[cnt++] = j;
+                }
+            }
+        });
+    }
+}
+#undef GN_KNN_INSERT
+#undef GN_KNN_FLUSH
 
 // ---------------------------------------------------------------- k-NN of large events: sort + pruned sweep
 // One workgroup per event that the sweep owns.  Key = 18-bit Morton code of the first (up to) three coordinates, quantised
@@ -1258,6 +1451,37 @@ hipError_t launch_minkowski_knn(const float* x, long long ldx, const int* space_
     else GN_MINK_LAUNCH_K(0)
 #undef GN_MINK_LAUNCH_K
 #undef GN_MINK_LAUNCH
+    return hipGetLastError();
+}
+
+// Radius graph: nbr[N, cap] and deg[N] (see radius_append_kernel).  Two launches on the tile plan, always: the second one
+// finds its work list empty when no centre is above the cap.  work: radius_work_ints(B, N) ints.
+long long radius_work_ints(int B, int N) { return 1 + (long long)N / KNN_TILE + B; }
+hipError_t launch_radius_graph(const float* x, long long ldx, const int* cols, int D, float r, const int* ptr,
+                               const int* tile_ptr, int B, int N, int cap, int* nbr, int* deg, int* work, hipStream_t st) {
+    if (N == 0 || B == 0) return hipSuccess;
+    KnnCols kc;
+    for (int d = 0; d < KNN_DMAX; ++d) kc.c[d] = d < D ? cols[d] : 0;
+    const float r2 = r * r;
+    hipError_t e = hipMemsetAsync(work, 0, sizeof(int), st);
+    if (e != hipSuccess) return e;
+    const long long tiles = (long long)N / KNN_TILE + B;
+    const dim3 grid((unsigned)tiles), block(KNN_TILE), grido((unsigned)(tiles < 2048 ? tiles : 2048));
+#define GN_RADIUS_LAUNCH(KM, DT_)                                                                               \
+    hipLaunchKernelGGL((radius_overflow_kernel<KM, DT_>), grido, block, 0, st, x, ldx, kc, D, r2, ptr, tile_ptr, B, N, cap, \
+                       nbr, deg, work);
+#define GN_RADIUS_LAUNCH_D(DT_)                                                                                 \
+    {                                                                                                           \
+        hipLaunchKernelGGL((radius_append_kernel<DT_>), grid, block, 0, st, x, ldx, kc, D, r2, ptr, tile_ptr, B, N, cap, \
+                           nbr, deg, work);                                                                     \
+        if (cap <= 8) GN_RADIUS_LAUNCH(8, DT_)                                                                  \
+        else if (cap <= 16) GN_RADIUS_LAUNCH(16, DT_)                                                           \
+        else GN_RADIUS_LAUNCH(32, DT_)                                                                          \
+    }
+    if (D == 3) GN_RADIUS_LAUNCH_D(3)
+    else GN_RADIUS_LAUNCH_D(0)
+#undef GN_RADIUS_LAUNCH_D
+#undef GN_RADIUS_LAUNCH
     return hipGetLastError();
 }
 

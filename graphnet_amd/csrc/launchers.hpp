@@ -11,6 +11,9 @@ long long knn_ws_bytes(int B, int N, int D);
 hipError_t launch_minkowski_knn(const float* x, long long ldx, const int* space_cols, int DS, int time_col, float c,
                                 float time_like_weight, const int* ptr, const int* tile_ptr, int B, int N, int k, int* nbr,
                                 hipStream_t st);
+hipError_t launch_radius_graph(const float* x, long long ldx, const int* cols, int D, float r, const int* ptr,
+                               const int* tile_ptr, int B, int N, int cap, int* nbr, int* deg, int* work, hipStream_t st);
+long long radius_work_ints(int B, int N);
 hipError_t launch_scan(const int* in, int* out, int n, int* tmp, int* total, hipStream_t st);
 hipError_t launch_ovf_compact(const int* ovf, int N, int* flag_pos, int* tmp, int* ovf_centre, int* ovf_src,
                               int* ovf_cnt, hipStream_t st);

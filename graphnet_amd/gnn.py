@@ -17,7 +17,7 @@ import torch
 from torch import Tensor
 
 from . import ops
-from .graphs import minkowski_record
+from .graphs import minkowski_record, radial_record
 from .model import REFERENCE, Model
 
 GLOBAL_POOLINGS = ("min", "max", "sum", "mean")
@@ -64,6 +64,15 @@ def _maybe(data: Any, key: str) -> Any:
         return data[key] if key in data else None
     except TypeError:
         return getattr(data, key, None)
+
+
+def _no_radial_record(data: Any, edge_index: Any, who: str) -> None:
+    """Only ``DynEdge`` builds the graph that ``RadialEdges`` recorded on a CPU ``Data``; the other backbones take it as
+    ``edge_index`` (the edge definition run on a device batch) and must not build k-NN in its place."""
+    if edge_index is None and radial_record(data) is not None:
+        raise NotImplementedError(
+            f"{who}: the batch carries the parameters of RadialEdges but no edge_index, and {who} does not build radius "
+            "graphs; apply RadialEdges to the batch on the device (it sets edge_index) or use DynEdge")
 
 
 def _subset_cols(subset: Union[slice, Sequence[int]], width: int) -> List[int]:
@@ -852,6 +861,12 @@ class DynEdge(GNN):
             plan = ops.knn_plan(ptr32, int(x.shape[0]))
             self.__dict__["_last_plan"] = plan
             return ops.minkowski_knn_graph(x, space_coords, time_coord, c, tlw, batch32, ptr32, k, plan=plan)
+        radial = radial_record(data)
+        if radial is not None:      # recorded by RadialEdges on a CPU Data: one launch for the whole batch, here
+            r, rcols, cap = radial
+            plan = ops.knn_plan(ptr32, int(x.shape[0]))
+            self.__dict__["_last_plan"] = plan
+            return ops.radius_graph(x, rcols, r, batch32, ptr32, cap, plan=plan)
         k, cols = self._nb_neighbours, self._graph_columns
         knn_k = _maybe(data, "knn_k")
         if knn_k is not None:       # recorded by KNNEdges on a CPU Data: same k / columns, built here
@@ -902,7 +917,8 @@ class DynEdge(GNN):
             from .step import DynEdgeStepFunction
             box: dict = {}
             if isinstance(_maybe(data, "nbr_table"), ops.NeighbourTable) or _maybe(data, "edge_index") is not None or \
-                    _maybe(data, "knn_k") is not None or _maybe(data, "mink_k") is not None:
+                    _maybe(data, "knn_k") is not None or _maybe(data, "mink_k") is not None or \
+                    _maybe(data, "radial_r") is not None:
                 box["table"] = self._layer0_graph(data, x, batch32, ptr32)      # the caller's graph (or its k / columns)
             out = DynEdgeStepFunction.apply(stepper, box, x.contiguous(), ptr32, batch32, n_pulses, *self._kernel_params())
             if self._add_global_variables_after_pooling:
@@ -992,6 +1008,7 @@ class DynEdgeJINST(GNN):
         x = x.to(torch.float32)
         ptr32, batch32, n_pulses = DynEdge._csr(self, data, x)
         ei = _maybe(data, "edge_index")
+        _no_radial_record(data, ei, type(self).__name__)
         g0 = (ops.table_from_edge_index(ei, int(x.shape[0]), 8) if ei is not None
               else ops.knn_graph(x, [0, 1, 2], batch32, ptr32, 8, strict=self._knn_strict, sweep=True))
         gv = ops.graph_globals(x, ptr32, g0, n_pulses)          # [mean_F | h_x h_y h_z h_t | log10 n]

@@ -1,7 +1,8 @@
-"""Graph definitions: ``GraphDefinition`` / ``KNNGraph`` / ``KNNEdges`` / ``MinkowskiKNNEdges`` / ``NodesAsPulses``.
+"""Graph definitions: ``GraphDefinition`` / ``KNNGraph`` / ``KNNEdges`` / ``MinkowskiKNNEdges`` / ``RadialEdges`` /
+``NodesAsPulses``.
 
 Host-side mirror of ``models/graphs/graph_definition.py:148-248``, ``graphs/graphs.py:13-58``,
-``graphs/edges/edges.py:47-80``, ``graphs/edges/minkowski.py:37-99`` and ``graphs/nodes/nodes.py:123-132``.
+``graphs/edges/edges.py:47-117``, ``graphs/edges/minkowski.py:37-99`` and ``graphs/nodes/nodes.py:123-132``.
 
 Difference by design: the reference builds k-NN edges on the CPU, one event
 at a time, inside DataLoader workers.  Here a CPU ``Data`` leaves ``edge_index`` unset and the
@@ -165,6 +166,80 @@ class MinkowskiKNNEdges(EdgeDefinition):
             batch32, ptr = _event_ptr(x, getattr(graph, "batch", None) if "batch" in graph else None)
             table = ops.minkowski_knn_graph(x.to(torch.float32), self.space_coords, self.time_coord, self.c,
                                             self.time_like_weight, batch32, ptr, self.nb_nearest_neighbours)
+            graph.edge_index = table.edge_index()
+        else:
+            graph.edge_index = None            # built on device for the whole batch by the backbone
+        return self._record(graph)
+
+
+# what RadialEdges records on a graph it does not build at once (same construction as MINKOWSKI_RECORD)
+RADIAL_RECORD = ("radial_r", "radial_columns", "radial_max")
+
+
+def radial_record(data: Any) -> Optional[Tuple[float, List[int], int]]:
+    """``(radius, columns, max_num_neighbours)`` recorded by :class:`RadialEdges` on ``data`` (a ``Data``, or a ``Batch``
+    where the scalars have become ``[B]`` tensors and the list a list of lists), or None."""
+    def get(name: str) -> Any:
+        try:
+            return data[name] if name in data else None
+        except TypeError:                                   # an object without __contains__ / __getitem__
+            return getattr(data, name, None)
+
+    def scalar(v: Any) -> Any:
+        return v.reshape(-1)[0].item() if isinstance(v, torch.Tensor) else v
+
+    r = get("radial_r")
+    if r is None:
+        return None
+    cols = get("radial_columns")
+    cols = list(cols[0]) if isinstance(cols, list) and cols and isinstance(cols[0], (list, tuple)) else list(cols)
+    return float(scalar(r)), [int(v) for v in cols], int(scalar(get("radial_max")))
+
+
+class RadialEdges(EdgeDefinition):
+    """Edges from every pulse of the same event inside a sphere of ``radius`` around each pulse, in the space of
+    ``columns`` (``graphs/edges/edges.py:83-117``; the first two arguments carry the reference's names, order and
+    defaults, the third exposes what the reference leaves at ``radius_graph``'s default ``max_num_neighbors = 32``).
+
+    For centre ``i`` and every other pulse ``j`` of its event, in fp32 without FMA contraction::
+
+        d2 = ((0 + e0*e0) + e1*e1) + ...      e = x[j, col] - x[i, col], columns left to right
+        r2 = r * r                            one fp32 multiply of the fp32-rounded radius
+        edge j -> i   iff   j != i  and  d2 < r2        (strict)
+
+    ``edge_index[0] = j``, ``edge_index[1] = i``, grouped by ``i``, ascending ``j`` inside a group; no self loops; a
+    pulse with a NaN or inf coordinate has no neighbours and is nobody's neighbour.  One ``gn_radius_graph`` call for
+    the whole batch; on a CPU ``Data`` the parameters are recorded (``RADIAL_RECORD``) and the backbone builds the
+    graph.  At most 32 neighbours per centre: that is the width of the edge kernels.
+
+    One deliberate difference from the reference:
+
+    * **Which neighbours survive the cap.**  Where more than ``max_num_neighbours`` pulses lie inside the radius,
+      ``torch_cluster`` keeps whichever its scan or tree meets first - a choice that depends on the storage order of the
+      pulses and differs between its CPU and CUDA builds.  Here the kept ones are the ``max_num_neighbours`` smallest in
+      the total order ``(d2, j)``, which does not depend on the order of the pulses; they are still stored ascending
+      by ``j``.  Wherever no centre exceeds the cap the edge set is that of any ``radius_graph``.
+    """
+
+    def __init__(self, radius: float, columns: List[int] = [0, 1, 2], max_num_neighbours: int = 32):
+        super().__init__()
+        self._radius = radius
+        self._columns = list(columns)
+        self._max_num_neighbours = max_num_neighbours
+
+    def _record(self, graph: Data) -> Data:
+        graph.radial_r = float(self._radius)
+        graph.radial_columns = [int(v) for v in self._columns]
+        graph.radial_max = int(self._max_num_neighbours)
+        return graph
+
+    def _construct_edges(self, graph: Data) -> Data:
+        x = graph.x
+        if x.is_cuda:
+            from . import ops
+            batch32, ptr = _event_ptr(x, getattr(graph, "batch", None) if "batch" in graph else None)
+            table = ops.radius_graph(x.to(torch.float32), self._columns, self._radius, batch32, ptr,
+                                     self._max_num_neighbours)
             graph.edge_index = table.edge_index()
         else:
             graph.edge_index = None            # built on device for the whole batch by the backbone
@@ -369,7 +444,7 @@ def _batch_from_raw(self: "GraphDefinition", events: "List[np.ndarray]", input_f
     if ed is not None and hasattr(ed, "_nb_nearest_neighbours"):
         b.knn_k = int(ed._nb_nearest_neighbours)
         b.knn_columns = list(ed._columns)
-    elif isinstance(ed, MinkowskiKNNEdges):
+    elif isinstance(ed, (MinkowskiKNNEdges, RadialEdges)):
         ed._record(b)
     for k, vals in (truth or {}).items():
         b[k] = torch.as_tensor(np.asarray([vals[i] for i in keep])).to(device)

@@ -271,12 +271,48 @@ def minkowski_knn_graph(x: Tensor, space_cols: Sequence[int], time_col: int, c: 
     return table
 
 
+def radius_graph(x: Tensor, cols: Sequence[int], r: float, batch: Tensor, ptr: Tensor, max_num_neighbours: int = 32,
+                 plan: Optional[Tensor] = None) -> NeighbourTable:
+    """Batched radius graph on ``x[:, cols]`` (fp32) inside each event (``gn_radius_graph``; the reference's
+    ``RadialEdges``, ``graphs/edges/edges.py:83-117``): edge ``j -> i`` iff ``j != i`` and ``d2 < r*r`` (strict), every
+    centre's sources ascending by index; a centre with more than ``max_num_neighbours`` in-radius pulses keeps the
+    nearest ones in the total order ``(d2, j)``.  Returns the strict table (no overflow column), as wide as the graph
+    needs - ``K = max(1, min(max_num_neighbours, deg.max()))``, one read-back - with the uncapped in-radius counts as
+    the attribute ``deg`` (int32 ``[N]``): ``(table.deg > max_num_neighbours).sum()`` centres hit the cap."""
+    if plan is None:
+        plan = knn_plan(ptr, int(x.shape[0]))
+    _need(x, torch.float32, "x"); _need(batch, torch.int32, "batch"); _need(ptr, torch.int32, "ptr")
+    N = int(x.shape[0])
+    ld = _rows(x, "x")
+    cap = int(max_num_neighbours)
+    if any(not 0 <= int(v) < int(x.shape[1]) for v in cols):
+        raise ValueError(f"radius_graph: columns {list(cols)} outside x[:, :{int(x.shape[1])}]")
+    nbr = torch.empty((N, max(cap, 0)), dtype=torch.int32, device=x.device)
+    deg = torch.empty(N, dtype=torch.int32, device=x.device)
+    c = (ctypes.c_int32 * len(cols))(*[int(v) for v in cols])
+    B = int(ptr.shape[0]) - 1
+    L = _lib.lib()
+    work = torch.empty(max(int(L.gn_radius_work_ints(B, N)), 1), dtype=torch.int32, device=x.device)
+    with _timed("radius_graph"):
+        _lib.check(L.gn_radius_graph(_p(x), ld, ctypes.cast(c, ctypes.c_void_p), len(cols), float(r), _p(ptr), _p(plan),
+                                     B, N, cap, _p(nbr), _p(deg), _p(work), _st()))
+    K = max(1, min(cap, int(deg.max().item()) if N and B > 0 else 0))
+    if N == 0 or B <= 0:
+        nbr = torch.full((N, K), -1, dtype=torch.int32, device=x.device)
+    table = _finish_table(nbr[:, :K].contiguous(), None, K)
+    table.event_ptr = ptr       # every edge stays inside its event: the reverse lists can be built event by event
+    table.deg = deg
+    return table
+
+
 def table_from_edge_index(edge_index: Tensor, N: int, K: int) -> NeighbourTable:
     """Loader-supplied ``edge_index`` -> neighbour table.  PyG's ``EdgeConv`` takes edges in any order and of any
     in-degree, so this does too: edges that are not grouped by ascending target are stable-sorted by target first,
     and the table is sized by the largest in-degree when that exceeds ``K + 1`` (a loader graph whose k differs
-    from the backbone's ``nb_neighbours``).  Indices outside ``[0, N)`` raise ``ValueError`` - the device pass
-    validates every entry before it writes anything."""
+    from the backbone's ``nb_neighbours``, or a radius graph): then every edge has a slot and the table is the strict
+    form without an overflow column - the table ``radius_graph`` builds for the same edges, so a backbone computes
+    the same bits from either.  Indices outside ``[0, N)`` raise ``ValueError`` - the device pass validates every
+    entry before it writes anything."""
     _need(edge_index, torch.int64, "edge_index")
     if edge_index.dim() != 2 or int(edge_index.shape[0]) != 2:
         raise ValueError("edge_index must be [2, E]")
@@ -285,20 +321,22 @@ def table_from_edge_index(edge_index: Tensor, N: int, K: int) -> NeighbourTable:
     E = int(edge_index.shape[1])
     first = torch.empty(max(N, 1), dtype=torch.int32, device=dev)
     err = torch.zeros(1, dtype=torch.int32, device=dev)
+    wide = False
     for _ in range(3):
         nbr = torch.empty((N, K), dtype=torch.int32, device=dev)
         ovf = torch.empty(max(N, 1), dtype=torch.int32, device=dev)
         _lib.check(_lib.lib().gn_edge_index_to_table(_p(edge_index), E, N, K, _p(first), _p(nbr), _p(ovf), _p(err), _st()))
         rc = int(err.item())
         if rc == 0:
-            return _finish_table(nbr, ovf[:N] if N else ovf, K)
+            return _finish_table(nbr, None if wide else ovf[:N] if N else ovf, K)
         if rc & 1:
             raise ValueError(f"edge_index holds node indices outside [0, {N})")
         if rc & 2:                               # any order is legal input: group by target, keep the order inside a group
             order = torch.argsort(edge_index[1], stable=True)
             edge_index = edge_index[:, order].contiguous()
         elif rc & 4:                             # in-degree above K + 1: size the table by the graph
-            K = int(torch.bincount(edge_index[1], minlength=max(N, 1)).max().item()) - 1
+            K = int(torch.bincount(edge_index[1], minlength=max(N, 1)).max().item())
+            wide = True
     raise RuntimeError("gn_edge_index_to_table: could not build the table")       # pragma: no cover
 
 

@@ -18,7 +18,7 @@ import torch
 from torch import Tensor
 
 from . import ops
-from .gnn import GNN, _ACT_NAMES, _ksegs, _maybe, _subset_cols
+from .gnn import GNN, _ACT_NAMES, _ksegs, _maybe, _no_radial_record, _subset_cols
 from .tito import _PostPoolFunction, _wt
 
 
@@ -286,6 +286,7 @@ class ParticleNeT(GNN):
         table = _maybe(data, "nbr_table")
         if not isinstance(table, ops.NeighbourTable):
             ei = _maybe(data, "edge_index")
+            _no_radial_record(data, ei, type(self).__name__)
             table = ops.table_from_edge_index(ei, N, self._nb_neighbours) if ei is not None else \
                 ops.knn_graph(x, self._graph_columns, batch32, ptr32, self._nb_neighbours, strict=self._knn_strict)
         plan = ops.knn_plan(ptr32, N)

@@ -24,7 +24,7 @@ import torch
 from torch import Tensor
 
 from . import ops
-from .gnn import GNN, _ksegs, _maybe
+from .gnn import GNN, _ksegs, _maybe, _no_radial_record
 
 _DT_PARAMS = 18   # tensors per DynTrans layer, see DynTrans.kernel_params
 
@@ -401,6 +401,7 @@ class DynEdgeTITO(GNN):
         table = _maybe(data, "nbr_table")
         if not isinstance(table, ops.NeighbourTable):
             ei = _maybe(data, "edge_index")
+            _no_radial_record(data, ei, type(self).__name__)
             table = ops.table_from_edge_index(ei, N, self._nb_neighbours) if ei is not None else \
                 ops.knn_graph(x, self._graph_columns, batch32, ptr32, self._nb_neighbours, strict=self._knn_strict)
         plan = ops.attention_plan(ptr32)

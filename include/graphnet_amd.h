@@ -72,6 +72,18 @@ int gn_knn_plan(const int32_t* ptr, int32_t B, int32_t* tile_ptr, void* stream);
 int gn_minkowski_knn_graph(const float* x, int64_t ldx, const int32_t* space_cols_host, int32_t DS, int32_t time_col,
                            float c, float time_like_weight, const int32_t* ptr, const int32_t* tile_ptr,
                            int32_t B, int32_t N, int32_t k, int32_t* nbr, void* stream);
+/* RadialEdges (models/graphs/edges/edges.py:83-117; radius_graph with max_num_neighbors = cap): edge j -> i iff j != i,
+ * both in one event, and d2 < r2 (strict), fp32 without FMA contraction:
+ *   d2 = ((0 + e0*e0) + e1*e1) + ...  e = x[j, col] - x[i, col], columns left to right;  r2 = r * r (one fp32 multiply)
+ * The centre is excluded by index; a pulse with a NaN or inf coordinate has no neighbours and is nobody's neighbour.
+ * nbr[N, cap]: every centre's sources ascending by j, -1 padded; a centre with more than cap in-radius pulses keeps the cap
+ * smallest in the total order (d2, j), still stored ascending by j.  deg[N]: the UNCAPPED in-radius count.
+ * cols: HOST int[D], 1 <= D <= 8, every column < ldx; 1 <= cap <= 32; r finite and > 0; tile_ptr: the plan of gn_knn_plan
+ * (required); work: gn_radius_work_ints(B, N) ints of scratch.  Events of any size are scanned exhaustively. */
+int64_t gn_radius_work_ints(int32_t B, int32_t N);
+int gn_radius_graph(const float* x, int64_t ldx, const int32_t* cols_host, int32_t D, float r, const int32_t* ptr,
+                    const int32_t* tile_ptr, int32_t B, int32_t N, int32_t cap, int32_t* nbr, int32_t* deg, int32_t* work,
+                    void* stream);
 
 /* exclusive scan; tmp: >= gn_scan_tmp_ints(n) ints; total (optional) receives the sum */
 int64_t gn_scan_tmp_ints(int64_t n);
