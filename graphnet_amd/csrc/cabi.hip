@@ -232,6 +232,12 @@ int gn_edgeconv_fwd(int32_t mode, const int32_t* nbr, const int32_t* ovf_centre,
 int32_t gn_edgeconv_dw2_slabs(int32_t mode, int32_t N, int32_t K, int32_t H1p, int32_t H2) {
     return gn::edge_dw2_slabs(mode, N, K, H1p, H2);
 }
+void gn_edgeconv_plan(int32_t mode, int32_t K, int64_t N, int32_t H1p, int32_t H1, int32_t H2, int32_t act, int32_t has_ovf,
+                      int32_t* plan_host) {
+    int out[8];
+    gn::edge_plan_query(mode, K, N, H1p, H1, H2, act, has_ovf != 0, out);
+    for (int i = 0; i < 8; ++i) plan_host[i] = out[i];
+}
 int gn_edgeconv_dw2(int32_t mode, const int32_t* nbr, const int32_t* ovf_centre, const int32_t* ovf_src,
                     const int32_t* ovf_cnt, int32_t N, int32_t K, const void* PQ, int32_t H1p, int32_t H1, int32_t H2,
                     const void* gout, int64_t ldg, void* saved, float* slab, float* db2_part, void* stream) {

@@ -17,6 +17,8 @@ int device_cus();
 hipError_t launch_edge_fwd_v2(int variant, const EdgeGraph& g, const void* PQ, int H1p, int H1, const void* W2p, const float* b2,
                               int H2, void* out, long long ldo, float* coords, const CoordCols& cc, unsigned char* maskB,
                               unsigned long long* tilevalid, int num_cus, hipStream_t st);
+// whether launch_edge_fwd_v2 takes the wave-specialised kernel for this layer (ldo: row pitch of `out` in elements)
+bool edge_fwd_v2_ws(int variant, const EdgeGraph& g, int H1p, int H1, int H2, long long ldo, const EdgeSwitches& sw);
 // slab: [parts][H2][H1], db2_part: [parts][H2] with parts = edge_dw2_v2_parts(); also writes hbits
 int edge_dw2_v2_parts(int N, int K, int H1p, int num_cus);
 hipError_t launch_edge_dw2_v2(int variant, const EdgeGraph& g, const void* PQ, int H1p, int H1, int H2, const void* gout,

@@ -908,6 +908,19 @@ int edge_leaky_supported(int mode, int K, int H1p, int H1, int H2) {
 int edge_max_supported(int mode, int K, int H1p, int H2) {
     return edge_plan(mode, K, 0, H1p, H1p, H2, 1, false, edge_switches()).supported;
 }
+// The plan of a layer as the launchers below take it, under this process's switches (host only: tests name the path they
+// mean to run and skip a shape outside a path's envelope by this answer).  out[8] = supported, persistent, variant, ovf,
+// compact_shape, compact_model, shape_persistent, and whether the persistent forward is the wave-specialised kernel
+// (`out` rows of pitch H2)
+void edge_plan_query(int mode, int K, long long N, int H1p, int H1, int H2, int act, bool has_ovf, int* out) {
+    const EdgeSwitches sw = edge_switches();
+    const EdgePlan p = edge_plan(mode, K, N, H1p, H1, H2, act, has_ovf, sw);
+    EdgeGraph g = {};
+    g.N = (int)N; g.K = K;
+    out[0] = p.supported; out[1] = p.persistent; out[2] = p.variant; out[3] = p.ovf;
+    out[4] = p.compact_shape; out[5] = p.compact_model; out[6] = p.shape_persistent;
+    out[7] = p.persistent && edge_fwd_v2_ws(p.variant, g, H1p, H1, H2, H2, sw);
+}
 
 // out is float in mode 0 and bf16 in mode 1; coords (optional, [N][8] fp32) receives the columns
 // coord_cols[0..ncoord) of the fp32 result (the next layer's k-NN coordinates).

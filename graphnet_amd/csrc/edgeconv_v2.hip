@@ -1498,6 +1498,13 @@ static bool fwd_offsets_ok(const EdgeGraph& g, int H1p, int H2, long long ld) {
 }
 // dW2: the same set for the pitch of g_out - its byte offsets N * ldg * 2 and N * H2 * 2 below 2^32 ARE the first term
 static bool dw2_offsets_ok(const EdgeGraph& g, int H1p, int H2, long long ldg) { return fwd_offsets_ok(g, H1p, H2, ldg); }
+// Whether the forward of this layer runs the wave-specialised kernel (launch_edge_fwd_v2 and the plan query of the ABI ask
+// here).  Hidden widths 337..352 (all 22 k-steps real) would need 4 more registers for the stationary W2 slice than
+// 3 waves per SIMD leave (the variant spilled 24 bytes): the relu variant takes the all-waves-gather kernel for them,
+// as it does with GN_EDGE_WS bit 0 clear or offsets beyond 32 bits; the other variants have no such kernel
+bool edge_fwd_v2_ws(int variant, const EdgeGraph& g, int H1p, int H1, int H2, long long ldo, const EdgeSwitches& sw) {
+    return fwd_offsets_ok(g, H1p, H2, ldo) && (variant != 0 || ((sw.edge_ws & 1) && (H1p == 128 || H1 <= 336)));
+}
 
 hipError_t launch_edge_fwd_v2(int variant, const EdgeGraph& g, const void* PQ, int H1p, int H1, const void* W2p, const float* b2,
                               int H2, void* out, long long ldo, float* coords, const CoordCols& cc, unsigned char* maskB,
@@ -1505,10 +1512,7 @@ hipError_t launch_edge_fwd_v2(int variant, const EdgeGraph& g, const void* PQ, i
     if (!v2_envelope(variant, g, H1p, H1, H2)) return hipErrorNotSupported;
     if (g.N == 0) return hipSuccess;
     const EdgeSwitches sw = edge_switches();
-    // hidden widths 337..352 (all 22 k-steps real) would need 4 more registers for the stationary W2 slice than
-    // 3 waves per SIMD leave (the variant spilled 24 bytes): the relu variant takes the all-waves-gather kernel for them,
-    // as it does with GN_EDGE_WS bit 0 clear or offsets beyond 32 bits; the other variants have no such kernel
-    const bool ws = fwd_offsets_ok(g, H1p, H2, ldo) && (variant != 0 || ((sw.edge_ws & 1) && (H1p == 128 || H1 <= 336)));
+    const bool ws = edge_fwd_v2_ws(variant, g, H1p, H1, H2, ldo, sw);
     if (!ws && variant != 0) return hipErrorNotSupported;
     const int ntiles = v2_tiles(g);
     const int grid = ntiles < num_cus ? ntiles : num_cus;

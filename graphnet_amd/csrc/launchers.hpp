@@ -64,6 +64,8 @@ hipError_t launch_edge_bwd(int mode, const EdgeGraph& g, const void* PQ, int H1p
                            long long ldg, const void* saved, const void* W2Tp, int H2p, void* dpre,
                            void* dP, long long ldp, hipStream_t st, int act = 0, int H1 = 0);
 int edge_leaky_supported(int mode, int K, int H1p, int H1, int H2);
+// out[8]: the EdgePlan fields in declaration order, then whether the persistent forward is wave-specialised (host only)
+void edge_plan_query(int mode, int K, long long N, int H1p, int H1, int H2, int act, bool has_ovf, int* out);
 int edge_dw2_slabs(int mode, int N, int K, int H1p, int H2);
 hipError_t launch_edge_dw2(int mode, const EdgeGraph& g, const void* PQ, int H1p, int H1, int H2, const void* gout,
                            long long ldg, void* saved, float* slab, float* db2_part, hipStream_t st, int act = 0);

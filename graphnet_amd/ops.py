@@ -531,6 +531,20 @@ def edgeconv_leaky_supported(mode: int, g: NeighbourTable, H1p: int, H1: int, H2
     return bool(_lib.lib().gn_edgeconv_leaky_supported(mode, g.K, H1p, H1, H2))
 
 
+EDGE_PLAN_FIELDS = ("supported", "persistent", "variant", "ovf", "compact_shape", "compact_model", "shape_persistent", "fwd_ws")
+
+
+def edgeconv_plan(mode: int, g: NeighbourTable, H1p: int, H1: int, H2: int, act: str = "relu") -> dict:
+    """Which kernels the passes of this layer run (``gn_edgeconv_plan``: the dispatch rule's own answer under this
+    process's ``GN_*`` switches; host only).  Keys: :data:`EDGE_PLAN_FIELDS` - ``persistent``: table rows on the persistent
+    bf16 kernels (else the tiled ones); ``ovf``: 0 no overflow list, 1 tiled overflow-row kernels, 2 the GEMM path;
+    ``compact_shape``: :func:`edgeconv_bwd_gather_compact` takes the layer; ``fwd_ws``: wave-specialised forward."""
+    out = (ctypes.c_int32 * 8)()
+    _lib.lib().gn_edgeconv_plan(mode, g.K, g.N, H1p, H1, H2, {"relu": 0, "leaky_relu": 2}[act], int(g.ovf_cnt is not None),
+                                ctypes.cast(out, ctypes.c_void_p))
+    return dict(zip(EDGE_PLAN_FIELDS, (int(v) for v in out)))
+
+
 def edgeconv_fwd(mode: int, g: NeighbourTable, PQ: Tensor, H1p: int, W2p: Tensor, b2: Tensor, H2: int,
                  out: Optional[Tensor] = None, coord_cols: Optional[Sequence[int]] = None, H1: Optional[int] = None,
                  act: str = "relu"):

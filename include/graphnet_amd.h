@@ -197,12 +197,26 @@ void gn_edgeconv_saved_offsets(int32_t N, int32_t K, int32_t H1p, int32_t H2, in
  * out: T[N, ldo].  coords (optional): fp32 [N][8], coords[i][d] = the fp32 value of output column
  * coord_cols_host[d], d < ncoord <= 8 — the coordinates DynEdgeConv re-runs k-NN on (layers.py:63-67),
  * kept in fp32 beside a bf16 `out`.  H1 <= H1p = real hidden width: columns H1..H1p-1 of P, Q and W2p are
- * zero padding (the packed layout), so the contraction may stop at H1. */
+ * zero padding (the packed layout), so the contraction may stop at H1.
+ * Rounding in bf16 mode: out[i] is the fp32 slot sum rounded once (RNE); a centre with an overflow row gets a second
+ * rounding, RNE(out[i] + m).  The two overflow paths differ there (gn_edgeconv_plan: ovf 1 / 2): the tiled overflow
+ * kernels add the fp32 message m, the GEMM path adds the message it stored as bf16 - one rounding more in out[i], and
+ * coords[i] (fp32 slot sum + m) then holds the bf16-rounded m, whereas it is the exact fp32 sum on the tiled path and for
+ * every centre without an overflow row.  The backward differs likewise (dP[i] += the fp32 resp. the bf16 dpre row). */
 int gn_edgeconv_fwd(int32_t mode, const int32_t* nbr, const int32_t* ovf_centre, const int32_t* ovf_src,
                     const int32_t* ovf_cnt, int32_t N, int32_t K, const void* PQ, int32_t H1p, int32_t H1,
                     const void* W2p, const float* b2, int32_t H2, void* out, int64_t ldo,
                     float* coords, const int32_t* coord_cols_host, int32_t ncoord,
                     void* saved, void* stream);
+/* Which kernels the three passes of one layer run (host only, no launch): the answer of the one dispatch rule
+ * (graphnet_amd/csrc/edge_plan.hpp) under this process's environment switches.  act: 0 = relu (the entries here), 1 = leaky
+ * relu + max (gn_edgeconv_max_*), 2 = leaky relu + add (gn_edgeconv_leaky_*); has_ovf: the graph has an overflow list.
+ * plan_host (HOST int32[8]) = { supported, persistent (table rows on the persistent bf16 kernels, else the tiled ones),
+ * variant, ovf (0 no overflow list, 1 tiled overflow-row kernels, 2 overflow rows on the GEMM kernels), compact_shape
+ * (gn_edgeconv_bwd_compact takes the layer), compact_model, shape_persistent, fwd_ws (the persistent forward is the
+ * wave-specialised kernel, for `out` rows of pitch H2) }. */
+void gn_edgeconv_plan(int32_t mode, int32_t K, int64_t N, int32_t H1p, int32_t H1, int32_t H2, int32_t act, int32_t has_ovf,
+                      int32_t* plan_host);
 /* dW2 / db2 partials: slab[nslab][H2][H1], db2_part[nslab][H2], nslab = gn_edgeconv_dw2_slabs();
  * reduce with gn_edgeconv_dw2_reduce (since ABI 6 NOT with gn_reduce_slabs: of the slabs reserved for overflow rows the
  * kernel writes only those whose row range holds overflow rows, and the reduction reads the count on the device).

@@ -143,6 +143,34 @@ def _plan_table(tmp_path, flags):
     return [tuple(int(v) for v in line.split()) for line in out.splitlines()]
 
 
+def test_plan_query_entry_answers_with_the_plan(lib_path):
+    """gn_edgeconv_plan (what the GPU tests name their path by) = the same table, under the switches of ITS process: a
+    fresh child per switch set (read once per process); the eighth field says whether the persistent forward is the
+    wave-specialised kernel (relu: GN_EDGE_WS bit 0, and H1 <= 336 or H1p = 128)."""
+    code = ("import ctypes, sys; l = ctypes.CDLL(sys.argv[1]); o = (ctypes.c_int32 * 8)()\n"
+            "for line in sys.stdin:\n"
+            "    a = [int(v) for v in line.split()]\n"
+            "    l.gn_edgeconv_plan(a[0], a[1], ctypes.c_int64(a[2]), *a[3:8], o); print(*o)\n")
+    switches = ("GN_DISABLE_V2", "GN_OVF_GEMM", "GN_DPRE_COMPACT", "GN_EDGE_WS")
+    for sw in sorted({sw for (_, sw), _ in CASES}):
+        rows = [(args, want) for (args, s), want in CASES if s == sw]
+        for edge_ws in (None, "0"):
+            env = {k: v for k, v in os.environ.items() if k not in switches}
+            env.update(GN_DISABLE_V2=str(sw[0]), GN_OVF_GEMM=str(sw[1]), GN_DPRE_COMPACT=str(sw[2]))
+            if edge_ws is not None:
+                env["GN_EDGE_WS"] = edge_ws
+            text = "".join(" ".join(str(v) for v in args) + "\n" for args, _ in rows)
+            out = subprocess.run([sys.executable, "-c", code, lib_path], env=env, input=text, stdout=subprocess.PIPE, text=True,
+                                 check=True).stdout
+            got = [tuple(int(v) for v in line.split()) for line in out.splitlines()]
+            assert len(got) == len(rows)
+            for (args, want), have in zip(rows, got):
+                _, _, N, H1p, H1, _, act, _ = args
+                ws = want[1] == PERS and (act != 0 or (edge_ws is None and (H1p == 128 or H1 <= 336)))
+                ws = ws and N * 4 * H1p < 2 ** 32                 # the wave-specialised kernel's 32-bit P|Q byte offsets
+                assert have == want + (int(ws),), (args, sw, edge_ws, have, want)
+
+
 @pytest.mark.parametrize("flags", [[], ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"]],
                          ids=["plain", "asan_ubsan"])
 def test_plan_table(tmp_path, flags):
