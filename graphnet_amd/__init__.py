@@ -8,7 +8,7 @@ needs a GPU; calling a device op without the built library raises ``RuntimeError
 from .data import Batch, Data, collate_fn, collator_sequence_buckleting  # noqa: F401
 from .detector import Detector, IceCube86, IceCubeDeepCore, IceCubeUpgrade, ORCA150SuperDense, Prometheus  # noqa: F401
 from .model import Model, ModelConfig  # noqa: F401
-from .graphs import GraphDefinition, KNNEdges, KNNGraph, MinkowskiKNNEdges, NodesAsPulses, RadialEdges  # noqa: F401
+from .graphs import GraphDefinition, KNNEdges, KNNGraph, MinkowskiKNNEdges, NodesAsPulses, PercentileClusters, RadialEdges  # noqa: F401
 from .gnn import GNN, DynEdge, DynEdgeConv, DynEdgeJINST  # noqa: F401
 from .tito import DynEdgeTITO, DynTrans  # noqa: F401
 from .particlenet import ParticleNeT  # noqa: F401

@@ -32,6 +32,9 @@ SIGNATURES = {
     "gn_minkowski_knn_graph": (I32, [P, I64, P, I32, I32, c_float, c_float, P, P, I32, I32, I32, P, P]),
     "gn_radius_work_ints": (I64, [I32, I32]),
     "gn_radius_graph": (I32, [P, I64, P, I32, c_float, P, P, I32, I32, I32, P, P, P, P]),
+    "gn_percentile_work_ints": (I64, [I32, I32]),
+    "gn_percentile_lds_max": (I32, []),
+    "gn_percentile_clusters": (I32, [P, I64, I32, P, I32, P, I32, P, I32, P, I32, I32, P, I64, P, P, P]),
     "gn_scan_tmp_ints": (I64, [I64]),
     "gn_scan_i32": (I32, [P, P, I32, P, P, P]),
     "gn_ovf_compact": (I32, [P, I32, P, P, P, P, P, P]),

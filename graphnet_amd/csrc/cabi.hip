@@ -94,6 +94,31 @@ int gn_radius_graph(const float* x, int64_t ldx, const int32_t* cols_host, int32
     return fail(gn::launch_radius_graph(x, ldx, cols_host, D, r, ptr, tile_ptr, B, N, cap, nbr, deg, work, S(stream)), me);
 }
 
+int64_t gn_percentile_work_ints(int32_t B, int32_t N) { return (B < 0 || N < 0) ? -1 : gn::percentile_work_ints(B, N); }
+int32_t gn_percentile_lds_max(void) { return gn::percentile_lds_max(); }
+// NS: the header's S (S() is the stream cast in this file)
+int gn_percentile_clusters(const float* x, int64_t ldx, int32_t N, const int32_t* ptr, int32_t B,
+                           const int32_t* cluster_cols_host, int32_t C, const int32_t* summ_cols_host, int32_t NS,
+                           const double* q_host, int32_t P, int32_t add_counts, float* out, int64_t ldo, int32_t* out_ptr,
+                           int32_t* work, void* stream) {
+    const char* me = "gn_percentile_clusters";
+    if (N < 0 || B < 0 || N > (1 << 28)) return bad(me, "need B >= 0 and 0 <= N <= 2^28");
+    if (C < 1 || C > 8 || NS < 1 || NS > 32 || P < 1 || P > 16) return bad(me, "need 1<=C<=8, 1<=S<=32, 1<=P<=16");
+    if (!cluster_cols_host || !summ_cols_host || !q_host) return bad(me, "need cluster_cols_host[C], summ_cols_host[S] and q_host[P]");
+    for (int p = 0; p < P; ++p) if (!(q_host[p] >= 0.0 && q_host[p] <= 1.0)) return bad(me, "need 0 <= q <= 1");
+    for (int i = 0; i < C + NS; ++i) {
+        const int ci = i < C ? cluster_cols_host[i] : summ_cols_host[i - C];
+        if (ci < 0 || ci >= ldx) return bad(me, "column out of range");
+        for (int j = 0; j < i; ++j)
+            if (ci == (j < C ? cluster_cols_host[j] : summ_cols_host[j - C])) return bad(me, "columns must be distinct");
+    }
+    if (ldo < (int64_t)C + (int64_t)NS * P + (add_counts ? 1 : 0)) return bad(me, "need ldo >= C + S*P + add_counts");
+    if (B > 0 && (!ptr || !out_ptr)) return bad(me, "need ptr[B+1] and out_ptr[B+1]");
+    if (N > 0 && B > 0 && (!x || !out || !work)) return bad(me, "need x, out[N, ldo] and work[gn_percentile_work_ints(B, N)]");
+    return fail(gn::launch_percentile_clusters(x, ldx, N, ptr, B, cluster_cols_host, C, summ_cols_host, NS, q_host, P,
+                                               add_counts ? 1 : 0, out, ldo, out_ptr, work, S(stream)), me);
+}
+
 int64_t gn_scan_tmp_ints(int64_t n) { return (n + 2047) / 2048 + 1; }
 int gn_scan_i32(const int32_t* in, int32_t* out, int32_t n, int32_t* tmp, int32_t* total, void* stream) {
     if (n < 0) return bad("gn_scan_i32", "n < 0");

@@ -38,6 +38,12 @@ hipError_t launch_concat_globals(const float* x, long long ldx, int F, const flo
 hipError_t launch_ptr_to_batch(const int* ptr, int B, int* batch, hipStream_t st);
 hipError_t launch_standardize(float* x, long long ldx, int N, int F, const int* nops, const int* op, const float* c,
                               hipStream_t st);
+// nodes.hip
+int percentile_lds_max();
+long long percentile_work_ints(int B, int N);
+hipError_t launch_percentile_clusters(const float* x, long long ldx, int N, const int* ptr, int B, const int* cluster_cols, int C,
+                                      const int* summ_cols, int S, const double* q, int P, int add_counts, float* out,
+                                      long long ldo, int* out_ptr, int* work, hipStream_t st);
 // gemm.hip
 hipError_t launch_gemm_nt(int mode, const Segs& a, int a_lowp, int M, const void* Wp, int Kp, int Npad, int Nreal,
                           const Epi& epi, void* C, long long ldc, int out_lowp, hipStream_t st);

@@ -1,0 +1,239 @@
+// graphnet_amd/csrc/nodes.hip — node definitions on the device (gfx950).
+//
+//   PercentileClusters (models/graphs/nodes/nodes.py:135-217, arithmetic of models/graphs/utils.py:12-172): the pulses of
+//   an event become one node per distinct tuple of the cluster columns; every other column is summarised by percentiles.
+//
+//   pct_cluster_kernel   one workgroup per event.  C stable bitonic passes over 64-bit keys (column key << 32 | position),
+//                        least significant cluster column (the FIRST of cluster_on) first, give the reference's lexsort
+//                        order; cluster heads are flagged, a workgroup scan turns the flags into each pulse's cluster rank.
+//                        Out (all in `work`): rank per pulse, first pulse and first sorted position per cluster, cluster
+//                        count per event.
+//   (launch_scan over the counts -> out_ptr)
+//   pct_summary_kernel   one workgroup per (event, summarised column): sort (rank << 32 | value key), NaN last inside its
+//                        cluster, then one thread per (cluster, percentile) does numpy's linear interpolation in fp64.
+//
+// Events of up to PCT_LDS_MAX pulses sort in LDS; larger ones run the same routine on their slice of `work` in global
+// memory (still one workgroup per event, so __syncthreads() orders the steps; correct, not fast).
+#include "launchers.hpp"
+
+namespace gn {
+
+constexpr int PCT_NT = 256;            // threads per workgroup
+constexpr int PCT_LDS_MAX = 4096;      // 32 KB of keys + 16 KB of permutation
+constexpr int PCT_CMAX = 8, PCT_SMAX = 32, PCT_PMAX = 16;
+constexpr unsigned int PCT_NAN_KEY = 0xffffffffu;       // after +inf (0xff800000)
+typedef unsigned long long u64;
+
+struct PctArgs { int cl[PCT_CMAX]; int sm[PCT_SMAX]; double q[PCT_PMAX]; };
+
+// order-preserving map of fp32 bits to unsigned
+__device__ __forceinline__ unsigned int pct_ord(unsigned int b) { return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }
+// cluster columns: -0.0 with +0.0, every NaN one key
+__device__ __forceinline__ unsigned int pct_cluster_key(float v) {
+    if (v != v) return PCT_NAN_KEY;
+    if (v == 0.0f) return 0x80000000u;
+    return pct_ord(__float_as_uint(v));
+}
+// summarised columns: the value's own bits (so that it can be read back from the key), every NaN one key
+__device__ __forceinline__ unsigned int pct_value_key(float v) { return v != v ? PCT_NAN_KEY : pct_ord(__float_as_uint(v)); }
+__device__ __forceinline__ float pct_key_value(unsigned int u) {
+    return __uint_as_float((u & 0x80000000u) ? (u ^ 0x80000000u) : ~u);
+}
+
+// ascending bitonic sort of keys[0..P), P a power of two >= 2; ends with a barrier
+template <typename KP>
+__device__ __forceinline__ void pct_sort(KP keys, int P, int tid) {
+    for (int kk = 2; kk <= P; kk <<= 1)
+        for (int j = kk >> 1; j > 0; j >>= 1) {
+            for (int t = tid; t < (P >> 1); t += PCT_NT) {
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+                const int l = i | j;
+                const u64 a = keys[i], b = keys[l];
+                if ((a > b) == ((i & kk) == 0)) { keys[i] = b; keys[l] = a; }
+            }
+            __syncthreads();
+        }
+}
+
+__device__ __forceinline__ int pct_pow2(int n) {
+    int P = 2;
+    while (P < n) P <<= 1;
+    return P;
+}
+
+template <typename KP, typename IP>
+__device__ __forceinline__ void pct_cluster_event(
+    KP keys, IP perm, int* part, const float* __restrict__ x, long long ldx, const PctArgs& a, int C, int lo, int n, int tid,
+    int* __restrict__ rank, int* __restrict__ first, int* __restrict__ start, int* __restrict__ cnt_ev)
+{
+    const int P = pct_pow2(n);
+    for (int i = tid; i < n; i += PCT_NT) perm[i] = i;
+    __syncthreads();
+    for (int c = 0; c < C; ++c) {
+        const int col = a.cl[c];
+        for (int i = tid; i < P; i += PCT_NT)
+            keys[i] = i < n ? ((u64)pct_cluster_key(x[(long long)(lo + perm[i]) * ldx + col]) << 32) | (unsigned int)i : ~0ull;
+        __syncthreads();
+        pct_sort(keys, P, tid);
+        for (int i = tid; i < n; i += PCT_NT) keys[i] = (u64)(unsigned int)perm[(int)(keys[i] & 0xffffffffu)];
+        __syncthreads();
+        for (int i = tid; i < n; i += PCT_NT) perm[i] = (int)keys[i];
+        __syncthreads();
+    }
+    // head flags (into keys), then a scan over contiguous chunks
+    for (int i = tid; i < n; i += PCT_NT) {
+        bool head = i == 0;
+        if (i > 0) {
+            const float* r0 = x + (long long)(lo + perm[i - 1]) * ldx;
+            const float* r1 = x + (long long)(lo + perm[i]) * ldx;
+            for (int c = 0; c < C; ++c) head = head || pct_cluster_key(r0[a.cl[c]]) != pct_cluster_key(r1[a.cl[c]]);
+        }
+        keys[i] = head ? 1ull : 0ull;
+    }
+    __syncthreads();
+    const int ipt = (n + PCT_NT - 1) / PCT_NT;
+    const int i0 = min(tid * ipt, n), i1 = min(i0 + ipt, n);
+    int mine = 0;
+    for (int i = i0; i < i1; ++i) mine += (int)keys[i];
+    part[tid] = mine;
+    __syncthreads();
+    for (int o = 1; o < PCT_NT; o <<= 1) {                 // inclusive scan of the 256 chunk totals
+        const int v = tid >= o ? part[tid - o] : 0;
+        __syncthreads();
+        part[tid] += v;
+        __syncthreads();
+    }
+    int run = part[tid] - mine;                            // heads before this chunk
+    for (int i = i0; i < i1; ++i) {
+        const int p = perm[i];
+        if (keys[i]) { first[lo + run] = lo + p; start[lo + run] = i; ++run; }
+        rank[lo + p] = run - 1;
+    }
+    if (tid == PCT_NT - 1) *cnt_ev = part[tid];
+}
+
+__global__ __launch_bounds__(PCT_NT) void pct_cluster_kernel(
+    const float* __restrict__ x, long long ldx, PctArgs a, int C, const int* __restrict__ ptr, int N,
+    int* __restrict__ rank, int* __restrict__ first, int* __restrict__ start, int* __restrict__ cnt,
+    u64* __restrict__ gkeys, int* __restrict__ gperm)
+{
+    __shared__ u64 skeys[PCT_LDS_MAX];
+    __shared__ int sperm[PCT_LDS_MAX];
+    __shared__ int part[PCT_NT];
+    const int ev = (int)blockIdx.x, tid = (int)threadIdx.x;
+    const int hi = min(ptr[ev + 1], N), lo = min(max(ptr[ev], 0), hi);
+    const int n = hi - lo;
+    if (n <= 0) { if (tid == 0) cnt[ev] = 0; return; }
+    if (n <= PCT_LDS_MAX) pct_cluster_event(skeys, sperm, part, x, ldx, a, C, lo, n, tid, rank, first, start, cnt + ev);
+    else pct_cluster_event(gkeys + 2ll * lo, gperm + lo, part, x, ldx, a, C, lo, n, tid, rank, first, start, cnt + ev);
+}
+
+// numpy's linear method on the ascending non-NaN values keys[a0 .. a0 + m) of one cluster
+template <typename KP>
+__device__ __forceinline__ float pct_lerp(KP keys, int a0, int m, double q) {
+#pragma clang fp contract(off)
+    if (m <= 0) return __builtin_nanf("");
+    const double h = (double)(m - 1) * q;
+    const double fl = __builtin_floor(h);
+    const int lo = (int)fl;
+    const int hi = min(lo + 1, m - 1);
+    const double g = h - fl;
+    const double a = (double)pct_key_value((unsigned int)(keys[a0 + lo] & 0xffffffffu));
+    const double b = (double)pct_key_value((unsigned int)(keys[a0 + hi] & 0xffffffffu));
+    const double d = b - a;
+    const double r = (g >= 0.5) ? b - d * (1.0 - g) : a + d * g;
+    return (float)r;
+}
+
+template <typename KP>
+__device__ __forceinline__ void pct_summary_column(
+    KP keys, const float* __restrict__ x, long long ldx, int col, const PctArgs& a, int Pq, int lo, int n, int ncl, int tid,
+    const int* __restrict__ rank, const int* __restrict__ start, float* __restrict__ o, long long ldo, long long rows_left)
+{
+    const int P = pct_pow2(n);
+    for (int i = tid; i < P; i += PCT_NT)
+        keys[i] = i < n ? ((u64)(unsigned int)rank[lo + i] << 32) | pct_value_key(x[(long long)(lo + i) * ldx + col]) : ~0ull;
+    __syncthreads();
+    pct_sort(keys, P, tid);
+    for (int idx = tid; idx < ncl * Pq; idx += PCT_NT) {
+        const int r = idx / Pq, p = idx - r * Pq;
+        if (r >= rows_left) continue;
+        const int s0 = start[lo + r], s1 = r + 1 < ncl ? start[lo + r + 1] : n;
+        int l = s0, h = s1;                                 // first NaN of the segment
+        while (l < h) {
+            const int mid = (l + h) >> 1;
+            if ((unsigned int)(keys[mid] & 0xffffffffu) == PCT_NAN_KEY) h = mid; else l = mid + 1;
+        }
+        o[(long long)r * ldo + p] = pct_lerp(keys, s0, l - s0, a.q[p]);
+    }
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(PCT_NT) void pct_summary_kernel(
+    const float* __restrict__ x, long long ldx, PctArgs a, int C, int S, int Pq, int add_counts, const int* __restrict__ ptr, int N,
+    const int* __restrict__ rank, const int* __restrict__ first, const int* __restrict__ start, const int* __restrict__ out_ptr,
+    float* __restrict__ out, long long ldo, u64* __restrict__ gkeys)
+{
+    __shared__ u64 skeys[PCT_LDS_MAX];
+    const int ev = (int)blockIdx.x, tid = (int)threadIdx.x;
+    const int hi = min(ptr[ev + 1], N), lo = min(max(ptr[ev], 0), hi);
+    const int n = hi - lo;
+    if (n <= 0) return;
+    const int ob = out_ptr[ev], ncl = out_ptr[ev + 1] - ob;
+    const long long rows_left = (long long)N - ob;          // out has N rows: nothing is written past them
+    float* o = out + (long long)ob * ldo;
+    if (blockIdx.y == 0) {
+        for (int idx = tid; idx < ncl * C; idx += PCT_NT) {
+            const int r = idx / C, c = idx - r * C;
+            if (r < rows_left) o[(long long)r * ldo + c] = x[(long long)first[lo + r] * ldx + a.cl[c]];
+        }
+        if (add_counts)
+            for (int r = tid; r < ncl; r += PCT_NT) {
+                const int count = (r + 1 < ncl ? start[lo + r + 1] : n) - start[lo + r];
+                if (r < rows_left) o[(long long)r * ldo + C + S * Pq] = count == 1 ? 0.0f : (float)log10((double)count);
+            }
+    }
+    if (n <= PCT_LDS_MAX) {
+        const int s = (int)blockIdx.y;
+        pct_summary_column(skeys, x, ldx, a.sm[s], a, Pq, lo, n, ncl, tid, rank, start, o + C + s * Pq, ldo, rows_left);
+    } else if (blockIdx.y == 0) {
+        for (int s = 0; s < S; ++s)
+            pct_summary_column(gkeys + 2ll * lo, x, ldx, a.sm[s], a, Pq, lo, n, ncl, tid, rank, start, o + C + s * Pq, ldo,
+                               rows_left);
+    }
+}
+
+// work: [keys 4N + perm N ints, only if N > PCT_LDS_MAX][rank N][first N][start N][cnt B][scan tmp]
+int percentile_lds_max() { return PCT_LDS_MAX; }
+static long long pct_big_ints(int N) { return N > PCT_LDS_MAX ? 5ll * N : 0; }
+static long long pct_scan_tmp(int B) { return ((long long)B + 2047) / 2048 + 1; }
+long long percentile_work_ints(int B, int N) { return pct_big_ints(N) + 3ll * N + B + pct_scan_tmp(B); }
+
+hipError_t launch_percentile_clusters(const float* x, long long ldx, int N, const int* ptr, int B, const int* cluster_cols, int C,
+                                      const int* summ_cols, int S, const double* q, int P, int add_counts, float* out,
+                                      long long ldo, int* out_ptr, int* work, hipStream_t st) {
+    if (B == 0) return hipSuccess;
+    if (N == 0) return hipMemsetAsync(out_ptr, 0, sizeof(int) * ((size_t)B + 1), st);
+    PctArgs a;
+    for (int i = 0; i < PCT_CMAX; ++i) a.cl[i] = i < C ? cluster_cols[i] : 0;
+    for (int i = 0; i < PCT_SMAX; ++i) a.sm[i] = i < S ? summ_cols[i] : 0;
+    for (int i = 0; i < PCT_PMAX; ++i) a.q[i] = i < P ? q[i] : 0.0;
+    u64* gkeys = reinterpret_cast<u64*>(work);              // 8-byte aligned: the first thing in `work`
+    int* gperm = work + 4ll * N;
+    int* rank = work + pct_big_ints(N);
+    int* first = rank + N;
+    int* start = first + N;
+    int* cnt = start + N;
+    int* tmp = cnt + B;
+    hipLaunchKernelGGL(pct_cluster_kernel, dim3((unsigned)B), dim3(PCT_NT), 0, st, x, ldx, a, C, ptr, N, rank, first, start, cnt,
+                       gkeys, gperm);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    e = launch_scan(cnt, out_ptr, B, tmp, out_ptr + B, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(pct_summary_kernel, dim3((unsigned)B, (unsigned)S), dim3(PCT_NT), 0, st, x, ldx, a, C, S, P, add_counts, ptr,
+                       N, rank, first, start, out_ptr, out, ldo, gkeys);
+    return hipGetLastError();
+}
+
+}  // namespace gn

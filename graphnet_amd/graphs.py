@@ -1,8 +1,8 @@
 """Graph definitions: ``GraphDefinition`` / ``KNNGraph`` / ``KNNEdges`` / ``MinkowskiKNNEdges`` / ``RadialEdges`` /
-``NodesAsPulses``.
+``NodesAsPulses`` / ``PercentileClusters``.
 
 Host-side mirror of ``models/graphs/graph_definition.py:148-248``, ``graphs/graphs.py:13-58``,
-``graphs/edges/edges.py:47-117``, ``graphs/edges/minkowski.py:37-99`` and ``graphs/nodes/nodes.py:123-132``.
+``graphs/edges/edges.py:47-117``, ``graphs/edges/minkowski.py:37-99`` and ``graphs/nodes/nodes.py:22-217``.
 
 Difference by design: the reference builds k-NN edges on the CPU, one event
 at a time, inside DataLoader workers.  Here a CPU ``Data`` leaves ``edge_index`` unset and the
@@ -24,12 +24,30 @@ from .model import Model
 
 
 class NodeDefinition(Model):
+    """Pulses -> nodes (``nodes/nodes.py:22-120``).  A subclass names its output columns in
+    ``_define_output_feature_names`` and builds the node matrix in ``_construct_nodes``."""
+
+    def __init__(self, input_feature_names: Optional[List[str]] = None) -> None:
+        super().__init__()
+        if input_feature_names is not None:
+            self.set_output_feature_names(input_feature_names)
+
     def forward(self, x: torch.Tensor):
         graph = self._construct_nodes(x)
-        return graph, self._output_feature_names
+        return graph, self._output_feature_names         # AttributeError while the names are not set
+
+    def set_number_of_inputs(self, input_feature_names: List[str]) -> None:
+        assert isinstance(input_feature_names, list)
+        self.nb_inputs = len(input_feature_names)
 
     def set_output_feature_names(self, input_feature_names: List[str]) -> None:
-        self._output_feature_names = list(input_feature_names)
+        self._output_feature_names = self._define_output_feature_names(list(input_feature_names))
+
+    def _define_output_feature_names(self, input_feature_names: List[str]) -> List[str]:
+        raise NotImplementedError
+
+    def _construct_nodes(self, x: torch.Tensor) -> Data:
+        raise NotImplementedError
 
     @property
     def nb_outputs(self) -> int:
@@ -39,8 +57,126 @@ class NodeDefinition(Model):
 class NodesAsPulses(NodeDefinition):
     """Each pulse is a node (``nodes/nodes.py:123-132``)."""
 
+    def _define_output_feature_names(self, input_feature_names: List[str]) -> List[str]:
+        return input_feature_names
+
     def _construct_nodes(self, x: torch.Tensor) -> Data:
         return Data(x=x)
+
+
+def _order_keys(v: np.ndarray, cluster: bool) -> np.ndarray:
+    """fp32 values -> uint32 keys that ascend with the values: every NaN one key after +inf; for a cluster column
+    ``-0.0`` is taken as ``+0.0``."""
+    v = np.ascontiguousarray(v, dtype=np.float32)
+    b = v.view(np.uint32)
+    k = np.where(b & np.uint32(0x80000000), ~b, b | np.uint32(0x80000000)).astype(np.uint32)
+    if cluster:
+        k[v == 0] = np.uint32(0x80000000)
+    k[np.isnan(v)] = np.uint32(0xFFFFFFFF)
+    return k
+
+
+def percentile_clusters_host(x: np.ndarray, cluster_cols: List[int], summ_cols: List[int], percentiles: List[float],
+                             add_counts: bool = True) -> np.ndarray:
+    """The contract of ``gn_percentile_clusters`` (``include/graphnet_amd.h``) for ONE event in vectorised numpy: fp32
+    ``[n, F]`` -> fp32 ``[M, C + S*P + add_counts]``.  Bit for bit what the kernels write, but for the counts column,
+    which is numpy's ``log10`` here."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    n, C, S, P = len(x), len(cluster_cols), len(summ_cols), len(percentiles)
+    W = C + S * P + (1 if add_counts else 0)
+    if n == 0:
+        return np.zeros((0, W), dtype=np.float32)
+    keys = [_order_keys(x[:, c], True) for c in cluster_cols]
+    order = np.lexsort(tuple(keys))                          # stable; the LAST cluster column is the most significant
+    sorted_keys = np.stack([k[order] for k in keys], axis=1)
+    head = np.ones(n, dtype=bool)
+    head[1:] = (sorted_keys[1:] != sorted_keys[:-1]).any(axis=1)
+    start = np.flatnonzero(head)
+    rank = np.empty(n, dtype=np.int64)
+    rank[order] = np.cumsum(head) - 1
+    M = len(start)
+    out = np.empty((M, W), dtype=np.float32)
+    out[:, :C] = x[order[start]][:, cluster_cols]            # a cluster's lowest-index pulse comes first in a stable sort
+    q = np.asarray(percentiles, dtype=np.float64) / 100
+    with np.errstate(invalid="ignore"):
+        for s, f in enumerate(summ_cols):
+            by_value = np.lexsort((_order_keys(x[:, f], False), rank))      # NaN last inside its cluster
+            vals = x[by_value, f].astype(np.float64)
+            m = np.add.reduceat((~np.isnan(vals)).astype(np.int64), start)
+            h = (m - 1)[:, None] * q[None, :]
+            fl = np.floor(h)
+            lo = np.maximum(fl.astype(np.int64), 0)
+            hi = np.maximum(np.minimum(lo + 1, (m - 1)[:, None]), 0)
+            g = h - fl
+            a, b = vals[start[:, None] + lo], vals[start[:, None] + hi]
+            d = b - a
+            r = np.where(g >= 0.5, b - d * (1 - g), a + d * g)
+            r[m == 0] = np.nan
+            out[:, C + s * P:C + (s + 1) * P] = r.astype(np.float32)
+    if add_counts:
+        out[:, -1] = np.log10(np.diff(np.append(start, n)).astype(np.float64)).astype(np.float32)
+    return out
+
+
+class PercentileClusters(NodeDefinition):
+    """One node per cluster of pulses with equal ``cluster_on`` features - with the DOM position, one node per DOM - and
+    every other feature summarised by ``percentiles`` (``nodes/nodes.py:135-217``; argument names, order and defaults
+    are the reference's).  Output columns: ``cluster_on + [f"{feature}_pct{p}" ...] + ["counts"]``; ``counts`` is
+    ``log10`` of the number of pulses of the cluster.
+
+    The arithmetic is defined operation by operation in ``include/graphnet_amd.h`` (``gn_percentile_clusters``): nodes
+    ascend in ``np.lexsort`` order of the cluster columns, percentiles are numpy's method "linear" over the cluster's
+    non-NaN values in fp64.  A device tensor takes one ``gn_percentile_clusters`` call; a CPU tensor takes
+    :func:`percentile_clusters_host`, the same contract in numpy (the loader path of the reference).  On the device a
+    whole batch is clustered by one call: ``GraphDefinition.batch_from_raw``.
+
+    Two definitions where the reference has none or differs:
+
+    * **NaN in a cluster column.**  All NaNs of a column are one value that sorts after ``+inf`` (the reference's
+      ``lexsort`` and ``unique`` disagree with each other there); ``-0.0`` clusters with ``+0.0``, as ``np.unique`` has it.
+    * **fp32.**  The node matrix is fp32 wherever it is built.  The reference's stand-alone call returns numpy's fp64
+      array, which ``GraphDefinition`` casts to ``dtype`` a line later.
+    """
+
+    def __init__(self, cluster_on: List[str], percentiles: List[int], add_counts: bool = True,
+                 input_feature_names: Optional[List[str]] = None) -> None:
+        self._cluster_on = list(cluster_on)
+        self._percentiles = list(percentiles)
+        self._add_counts = add_counts
+        super().__init__(input_feature_names=input_feature_names)
+
+    def _define_output_feature_names(self, input_feature_names: List[str]) -> List[str]:
+        summarised = [f for f in input_feature_names if f not in self._cluster_on]
+        self._cluster_indices = [input_feature_names.index(f) for f in self._cluster_on]
+        self._summarization_indices = [input_feature_names.index(f) for f in summarised]
+        names = list(self._cluster_on) + [f"{f}_pct{p}" for f in summarised for p in self._percentiles]
+        return names + ["counts"] if self._add_counts else names
+
+    def _indices(self) -> Tuple[List[int], List[int]]:
+        if not hasattr(self, "_summarization_indices"):
+            raise AttributeError(f"{self.__class__.__name__} was instantiated without `input_feature_names` and they "
+                                 "were not set before this call; outside a GraphDefinition pass `input_feature_names`")
+        return self._cluster_indices, self._summarization_indices
+
+    def cluster_batch(self, x: torch.Tensor, ptr: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``(nodes fp32 [M, W], node_ptr int32 [B + 1])`` of the events ``ptr`` marks in ``x``: one device call, or
+        the host path event by event for a CPU tensor."""
+        cl, sm = self._indices()
+        if x.is_cuda:
+            from . import ops
+            return ops.percentile_clusters(x.to(torch.float32), ptr.to(torch.int32), cl, sm, self._percentiles,
+                                           self._add_counts)
+        xn, bounds = x.detach().to(torch.float32).numpy(), ptr.tolist()
+        parts = [percentile_clusters_host(xn[lo:hi], cl, sm, self._percentiles, self._add_counts)
+                 for lo, hi in zip(bounds[:-1], bounds[1:])]
+        node_ptr = np.zeros(len(bounds), dtype=np.int32)
+        node_ptr[1:] = np.cumsum([len(p) for p in parts])
+        nodes = np.concatenate(parts, axis=0) if parts else np.zeros((0, self.nb_outputs), dtype=np.float32)
+        return torch.from_numpy(nodes), torch.from_numpy(node_ptr)
+
+    def _construct_nodes(self, x: torch.Tensor) -> Data:
+        ptr = torch.tensor([0, int(x.shape[0])], dtype=torch.int32, device=x.device)
+        return Data(x=self.cluster_batch(x, ptr)[0])
 
 
 class EdgeDefinition(Model):
@@ -285,6 +421,7 @@ class GraphDefinition(Model):
         if input_feature_names is None:
             input_feature_names = list(detector.feature_map().keys())
         self._input_feature_names = list(input_feature_names)
+        self._node_definition.set_number_of_inputs(self._input_feature_names)
         self._node_definition.set_output_feature_names(self._input_feature_names)
         self.output_feature_names = list(getattr(self._node_definition, "_output_feature_names",
                                                  self._input_feature_names))
@@ -417,7 +554,9 @@ def _batch_from_raw(self: "GraphDefinition", events: "List[np.ndarray]", input_f
     host-to-device copy -> the detector's standardisation as one kernel over the whole batch
     (``gn_standardize``, bit-identical to the per-event host expressions) -> ``Batch`` without edges (the backbone
     builds the layer-1 k-NN on device, ``gn_knn_graph``).  Events with <= 1 pulse are dropped, as ``collate_fn``
-    does.  ``truth``: name -> per-event sequence (filtered alongside)."""
+    does.  With a :class:`PercentileClusters` node definition the standardised batch goes through one
+    ``gn_percentile_clusters`` call: ``x`` / ``ptr`` / ``batch`` describe the clusters, ``n_pulses`` the raw pulses.
+    ``truth``: name -> per-event sequence (filtered alongside)."""
     from .data import Batch
     keep = [i for i, e in enumerate(events) if len(e) > 1]
     sizes = np.asarray([len(events[i]) for i in keep], dtype=np.int64)
@@ -434,12 +573,25 @@ def _batch_from_raw(self: "GraphDefinition", events: "List[np.ndarray]", input_f
     x = self._detector(x, input_feature_names)
     if self._sort_by is not None:
         raise NotImplementedError("graphnet_amd: sort_by is a per-event host option; use the per-event path")
-    b = Batch(x=x)
-    ptr_t = torch.from_numpy(ptr)
-    b.ptr = ptr_t.to(device)
+    nd = self._node_definition
     n_pulses = torch.from_numpy(sizes).to(torch.int32)
-    b.n_pulses = n_pulses.to(device)
-    b.batch = torch.repeat_interleave(torch.arange(len(keep), dtype=torch.int64), torch.from_numpy(sizes)).to(device)
+    if isinstance(nd, PercentileClusters):
+        # one clustering call over the whole batch: ptr / batch describe nodes from here on, n_pulses stays pulses
+        nodes, node_ptr = nd.cluster_batch(x, torch.from_numpy(ptr).to(torch.int32).to(x.device))
+        b = Batch(x=nodes.type(self.dtype))
+        b.ptr = node_ptr.to(torch.int64)
+        b.n_pulses = n_pulses.to(device)
+        b.batch = torch.repeat_interleave(torch.arange(len(keep), dtype=torch.int64, device=b.ptr.device),
+                                          b.ptr[1:] - b.ptr[:-1], output_size=int(nodes.shape[0]))
+    elif isinstance(nd, NodesAsPulses):
+        b = Batch(x=x)
+        ptr_t = torch.from_numpy(ptr)
+        b.ptr = ptr_t.to(device)
+        b.n_pulses = n_pulses.to(device)
+        b.batch = torch.repeat_interleave(torch.arange(len(keep), dtype=torch.int64), torch.from_numpy(sizes)).to(device)
+    else:
+        raise NotImplementedError(f"graphnet_amd: batch_from_raw builds NodesAsPulses and PercentileClusters nodes, not "
+                                  f"{nd.__class__.__name__}; use the per-event path")
     ed = self._edge_definition
     if ed is not None and hasattr(ed, "_nb_nearest_neighbours"):
         b.knn_k = int(ed._nb_nearest_neighbours)

@@ -305,6 +305,45 @@ def radius_graph(x: Tensor, cols: Sequence[int], r: float, batch: Tensor, ptr: T
     return table
 
 
+def percentile_clusters(x: Tensor, ptr: Tensor, cluster_cols: Sequence[int], summ_cols: Sequence[int],
+                        percentiles: Sequence[float], add_counts: bool = True,
+                        out_pitch: Optional[int] = None) -> Tuple[Tensor, Tensor]:
+    """Batched DOM clustering with percentile features (``gn_percentile_clusters``; the reference's
+    ``PercentileClusters``, ``graphs/nodes/nodes.py:135-217``): inside each event of ``ptr`` (int32 ``[B + 1]``) the rows
+    of ``x`` (fp32) with equal ``cluster_cols`` become one node ``[cluster columns | percentiles of every column of
+    summ_cols | log10(count)]``, nodes ascending in the reference's lexsort order.  Returns ``(nodes[M, W], node_ptr int32
+    [B + 1])``: one call, one read-back (``M``); ``nodes`` is a view of the first ``M`` rows of the ``N``-row buffer the
+    kernel wrote (``out_pitch``: its row pitch, ``W`` by default).  The contract is spelled out in
+    ``include/graphnet_amd.h``."""
+    _need(x, torch.float32, "x"); _need(ptr, torch.int32, "ptr")
+    N, B = int(x.shape[0]), int(ptr.shape[0]) - 1
+    C, S, P = len(cluster_cols), len(summ_cols), len(percentiles)
+    W = C + S * P + (1 if add_counts else 0)
+    ldo = W if out_pitch is None else int(out_pitch)
+    if ldo < W:
+        raise ValueError(f"percentile_clusters: out_pitch {ldo} < {W} columns")
+    if any(not 0 <= int(v) < int(x.shape[1]) for v in list(cluster_cols) + list(summ_cols)):
+        raise ValueError(f"percentile_clusters: columns {list(cluster_cols)} / {list(summ_cols)} outside x[:, :{int(x.shape[1])}]")
+    if N == 0 or B <= 0:
+        return (torch.empty((0, ldo), dtype=torch.float32, device=x.device)[:, :W],
+                torch.zeros(max(B, 0) + 1, dtype=torch.int32, device=x.device))
+    ld = _rows(x, "x")
+    cl = (ctypes.c_int32 * C)(*[int(v) for v in cluster_cols])
+    sm = (ctypes.c_int32 * S)(*[int(v) for v in summ_cols])
+    q = (ctypes.c_double * P)(*[float(v) / 100.0 for v in percentiles])      # numpy's true_divide(q, 100), fp64
+    L = _lib.lib()
+    out = torch.empty((N, ldo), dtype=torch.float32, device=x.device)
+    node_ptr = torch.empty(B + 1, dtype=torch.int32, device=x.device)
+    # int64 elements: the sort keys at the front of `work` are 8 bytes wide
+    work = torch.empty((int(L.gn_percentile_work_ints(B, N)) + 1) // 2, dtype=torch.int64, device=x.device)
+    with _timed("percentile_clusters"):
+        _lib.check(L.gn_percentile_clusters(_p(x), ld, N, _p(ptr), B, ctypes.cast(cl, ctypes.c_void_p), C,
+                                            ctypes.cast(sm, ctypes.c_void_p), S, ctypes.cast(q, ctypes.c_void_p), P,
+                                            1 if add_counts else 0, _p(out), ldo, _p(node_ptr), _p(work), _st()))
+    M = int(node_ptr[B].item())
+    return out[:M, :W], node_ptr
+
+
 def table_from_edge_index(edge_index: Tensor, N: int, K: int) -> NeighbourTable:
     """Loader-supplied ``edge_index`` -> neighbour table.  PyG's ``EdgeConv`` takes edges in any order and of any
     in-degree, so this does too: edges that are not grouped by ascending target are stable-sorted by target first,

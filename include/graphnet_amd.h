@@ -85,6 +85,28 @@ int gn_radius_graph(const float* x, int64_t ldx, const int32_t* cols_host, int32
                     const int32_t* tile_ptr, int32_t B, int32_t N, int32_t cap, int32_t* nbr, int32_t* deg, int32_t* work,
                     void* stream);
 
+/* PercentileClusters (models/graphs/nodes/nodes.py:135-217): one node per distinct tuple of the cluster columns inside each
+ * event, every summarised column reduced to P percentiles, fp32 in and out.
+ *   key of a cluster value: its fp32 bits with -0.0 taken as +0.0 and every NaN as ONE value after +inf; two pulses share a
+ *     cluster iff all C keys are equal (NaNs cluster together: a definition).
+ *   row order: clusters ascend lexicographically, the LAST cluster column most significant (np.lexsort of the columns).
+ *   row = [x[first, c_0 .. c_{C-1}] | for f in summ_cols, for p: pct(f, p) | log10(count) if add_counts], first = the
+ *     lowest-index pulse of the cluster, W = C + S*P + add_counts columns.
+ *   pct: v[0..m) = the cluster's non-NaN values of f, ascending, as fp64 (m = 0 -> NaN); fp64 without FMA contraction:
+ *     h = (m-1)*q; lo = floor(h); hi = min(lo+1, m-1); g = h - lo; d = v[hi] - v[lo];
+ *     r = g >= 0.5 ? v[hi] - d*(1-g) : v[lo] + d*g;  out = (float) r        (numpy's method "linear"; q = percentile / 100)
+ *   count: pulses of the cluster (NaN values included); the column is (float) log10((double) count), exactly 0 for 1.
+ * out[N, ldo]: room for N rows (never more clusters than pulses), the first out_ptr[B] are written; out_ptr[B+1]: cluster
+ * offsets per event, out_ptr[B] = node count.  cluster_cols / summ_cols / q: HOST arrays; 1 <= C <= 8, 1 <= S <= 32,
+ * 1 <= P <= 16, 0 <= q <= 1, columns distinct and < ldx, ldo >= W, N <= 2^28.  work: gn_percentile_work_ints(B, N) ints, 8-byte
+ * aligned.  Events of up to gn_percentile_lds_max() pulses sort in LDS, larger ones in `work` (correct, not fast). */
+int64_t gn_percentile_work_ints(int32_t B, int32_t N);
+int32_t gn_percentile_lds_max(void);   /* largest event sorted in LDS */
+int gn_percentile_clusters(const float* x, int64_t ldx, int32_t N, const int32_t* ptr, int32_t B,
+                           const int32_t* cluster_cols_host, int32_t C, const int32_t* summ_cols_host, int32_t S,
+                           const double* q_host, int32_t P, int32_t add_counts,
+                           float* out, int64_t ldo, int32_t* out_ptr, int32_t* work, void* stream);
+
 /* exclusive scan; tmp: >= gn_scan_tmp_ints(n) ints; total (optional) receives the sum */
 int64_t gn_scan_tmp_ints(int64_t n);
 int gn_scan_i32(const int32_t* in, int32_t* out, int32_t n, int32_t* tmp, int32_t* total, void* stream);
