@@ -8,9 +8,12 @@ needs a GPU; calling a device op without the built library raises ``RuntimeError
 from .data import Batch, Data, collate_fn, collator_sequence_buckleting  # noqa: F401
 from .detector import Detector, IceCube86, IceCubeDeepCore, IceCubeUpgrade, ORCA150SuperDense, Prometheus  # noqa: F401
 from .model import Model, ModelConfig  # noqa: F401
-from .graphs import GraphDefinition, KNNEdges, KNNGraph, MinkowskiKNNEdges, NodesAsPulses, PercentileClusters, RadialEdges  # noqa: F401
+from .graphs import (  # noqa: F401
+    GraphDefinition, KNNEdges, KNNGraph, MinkowskiKNNEdges, NodeAsDOMTimeSeries, NodesAsPulses, PercentileClusters, RadialEdges,
+)
 from .gnn import GNN, DynEdge, DynEdgeConv, DynEdgeJINST  # noqa: F401
 from .tito import DynEdgeTITO, DynTrans  # noqa: F401
+from .rnn import Node_RNN, RNN_TITO  # noqa: F401
 from .particlenet import ParticleNeT  # noqa: F401
 from .standard_model import (  # noqa: F401
     BinaryClassificationTask, BinaryClassificationTaskLogits, BinaryCrossEntropyLoss, DirectionReconstructionWithKappa,

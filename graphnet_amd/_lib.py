@@ -35,6 +35,14 @@ SIGNATURES = {
     "gn_percentile_work_ints": (I64, [I32, I32]),
     "gn_percentile_lds_max": (I32, []),
     "gn_percentile_clusters": (I32, [P, I64, I32, P, I32, P, I32, P, I32, P, I32, I32, P, I64, P, P, P]),
+    "gn_dom_time_series_work_ints": (I64, [I32, I32]),
+    "gn_dom_time_series": (I32, [P, I64, I32, I32, P, I32, P, I32, I32, I32, P, I64, P, P, P, P]),
+    "gn_gru_supported": (I32, [I32, I32]),
+    "gn_gru_saved_floats": (I64, [I32, I32]),
+    "gn_gru_bwd_work_floats": (I64, [I32, I32, I32]),
+    "gn_gru_series_fwd": (I32, [P, I64, I32, I32, P, I32, I32, P, P, P, P, P, P, P]),
+    "gn_gru_series_bwd": (I32, [P, P, P, I64, I32, I32, P, I32, I32, P, P, P, P, P, P, P]),
+    "gn_dom_series_summary": (I32, [P, I64, I32, I32, P, I32, I32, P, I64, P]),
     "gn_scan_tmp_ints": (I64, [I64]),
     "gn_scan_i32": (I32, [P, P, I32, P, P, P]),
     "gn_ovf_compact": (I32, [P, I32, P, P, P, P, P, P]),

@@ -119,6 +119,70 @@ int gn_percentile_clusters(const float* x, int64_t ldx, int32_t N, const int32_t
                                                add_counts ? 1 : 0, out, ldo, out_ptr, work, S(stream)), me);
 }
 
+int64_t gn_dom_time_series_work_ints(int32_t B, int32_t N) { return (B < 0 || N < 0) ? -1 : gn::dom_time_series_work_ints(B, N); }
+int gn_dom_time_series(const float* x, int64_t ldx, int32_t F, int32_t N, const int32_t* ptr, int32_t B,
+                       const int32_t* id_cols_host, int32_t C, int32_t time_col, int32_t charge_col, float* out, int64_t ldo,
+                       int32_t* series_ptr, int32_t* dom_ptr, int32_t* work, void* stream) {
+    const char* me = "gn_dom_time_series";
+    if (N < 0 || B < 0 || N > (1 << 28)) return bad(me, "need B >= 0 and 0 <= N <= 2^28");
+    if (F < 1 || F > ldx) return bad(me, "need 1 <= F <= ldx");
+    if (C < 1 || C > 8 || !id_cols_host) return bad(me, "need id_cols_host[C], 1<=C<=8");
+    if (time_col < 0 || time_col >= F || charge_col < -1 || charge_col >= F || charge_col == time_col)
+        return bad(me, "time / charge column out of range (charge_col = -1: none)");
+    for (int i = 0; i < C; ++i) {
+        const int ci = id_cols_host[i];
+        if (ci < 0 || ci >= F) return bad(me, "column out of range");
+        if (ci == time_col || ci == charge_col) return bad(me, "columns must be distinct");
+        for (int j = 0; j < i; ++j) if (ci == id_cols_host[j]) return bad(me, "columns must be distinct");
+    }
+    if (ldo < (int64_t)F + (charge_col < 0 ? 1 : 0) + 1) return bad(me, "need ldo >= F + (charge_col < 0) + 1");
+    if (!series_ptr) return bad(me, "need series_ptr[N+1]");
+    if (B > 0 && (!ptr || !dom_ptr)) return bad(me, "need ptr[B+1] and dom_ptr[B+1]");
+    if (N > 0 && B > 0 && (!x || !out || !work)) return bad(me, "need x, out[N, ldo] and work[gn_dom_time_series_work_ints(B, N)]");
+    return fail(gn::launch_dom_time_series(x, ldx, F, N, ptr, B, id_cols_host, C, time_col, charge_col, out, ldo, series_ptr,
+                                           dom_ptr, work, S(stream)), me);
+}
+
+int32_t gn_gru_supported(int32_t I, int32_t H) { return gn::gru_supported(I, H); }
+int64_t gn_gru_saved_floats(int32_t T, int32_t H) { return (T < 0 || H < 1) ? -1 : gn::gru_saved_floats(T, H); }
+int64_t gn_gru_bwd_work_floats(int32_t T, int32_t I, int32_t H) {
+    return (T < 0 || !gn::gru_supported(I, H)) ? -1 : gn::gru_bwd_work_floats(T, I, H);
+}
+int gn_gru_series_fwd(const float* xs, int64_t ldx, int32_t T, int32_t I, const int32_t* series_ptr, int32_t M, int32_t H,
+                      const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, float* out, float* saved,
+                      void* stream) {
+    const char* me = "gn_gru_series_fwd";
+    if (!gn::gru_supported(I, H)) return bad(me, "outside the envelope: need 1<=I<=32, 4<=H<=64, H%4==0 (gn_gru_supported)");
+    if (T < 0 || M < 0 || M > T || ldx < I) return bad(me, "need 0 <= M <= T (no empty series) and ldx >= I");
+    if (!w_ih || !w_hh || !b_ih || !b_hh) return bad(me, "need weight_ih[3H, I], weight_hh[3H, H], bias_ih[3H], bias_hh[3H]");
+    if (M > 0 && (!xs || !series_ptr || !out)) return bad(me, "need xs[T, ldx], series_ptr[M+1] and out[M, H]");
+    if (reinterpret_cast<uintptr_t>(saved) & 15) return bad(me, "saved must be 16-byte aligned");
+    return fail(gn::launch_gru_series_fwd(xs, ldx, T, I, series_ptr, M, H, w_ih, w_hh, b_ih, b_hh, out, saved, S(stream)), me);
+}
+int gn_gru_series_bwd(const float* dout, const float* saved, const float* xs, int64_t ldx, int32_t T, int32_t I,
+                      const int32_t* series_ptr, int32_t M, int32_t H, const float* w_hh, float* dw_ih, float* db_ih,
+                      float* dw_hh, float* db_hh, float* work, void* stream) {
+    const char* me = "gn_gru_series_bwd";
+    if (!gn::gru_supported(I, H)) return bad(me, "outside the envelope: need 1<=I<=32, 4<=H<=64, H%4==0 (gn_gru_supported)");
+    if (T < 0 || M < 0 || M > T || ldx < I) return bad(me, "need 0 <= M <= T (no empty series) and ldx >= I");
+    if (!w_hh || !dw_ih || !db_ih || !dw_hh || !db_hh) return bad(me, "need weight_hh and the four gradient buffers");
+    if (M > 0 && (!dout || !saved || !xs || !series_ptr || !work))
+        return bad(me, "need dout[M, H], saved, xs[T, ldx], series_ptr[M+1] and work[gn_gru_bwd_work_floats(T, I, H)]");
+    if ((reinterpret_cast<uintptr_t>(saved) & 15) || (reinterpret_cast<uintptr_t>(work) & 15))
+        return bad(me, "saved and work must be 16-byte aligned");
+    return fail(gn::launch_gru_series_bwd(dout, saved, xs, ldx, T, I, series_ptr, M, H, w_hh, dw_ih, db_ih, dw_hh, db_hh, work,
+                                          S(stream)), me);
+}
+int gn_dom_series_summary(const float* x, int64_t ldx, int32_t F, int32_t N, const int32_t* series_ptr, int32_t M,
+                          int32_t charge_col, float* out, int64_t ldo, void* stream) {
+    const char* me = "gn_dom_series_summary";
+    if (N < 0 || M < 0 || M > N) return bad(me, "need 0 <= M <= N");
+    if (F < 1 || F > ldx || ldo < F) return bad(me, "need 1 <= F <= ldx and ldo >= F");
+    if (charge_col < 0 || charge_col >= F) return bad(me, "charge column out of range");
+    if (M > 0 && (!x || !series_ptr || !out)) return bad(me, "need x[N, ldx], series_ptr[M+1] and out[M, ldo]");
+    return fail(gn::launch_dom_series_summary(x, ldx, F, N, series_ptr, M, charge_col, out, ldo, S(stream)), me);
+}
+
 int64_t gn_scan_tmp_ints(int64_t n) { return (n + 2047) / 2048 + 1; }
 int gn_scan_i32(const int32_t* in, int32_t* out, int32_t n, int32_t* tmp, int32_t* total, void* stream) {
     if (n < 0) return bad("gn_scan_i32", "n < 0");

@@ -44,6 +44,22 @@ long long percentile_work_ints(int B, int N);
 hipError_t launch_percentile_clusters(const float* x, long long ldx, int N, const int* ptr, int B, const int* cluster_cols, int C,
                                       const int* summ_cols, int S, const double* q, int P, int add_counts, float* out,
                                       long long ldo, int* out_ptr, int* work, hipStream_t st);
+long long dom_time_series_work_ints(int B, int N);
+hipError_t launch_dom_time_series(const float* x, long long ldx, int F, int N, const int* ptr, int B, const int* id_cols, int C,
+                                  int time_col, int charge_col, float* out, long long ldo, int* series_ptr, int* dom_ptr,
+                                  int* work, hipStream_t st);
+// rnn.hip
+int gru_supported(int I, int H);
+long long gru_saved_floats(int T, int H);
+long long gru_bwd_work_floats(int T, int I, int H);
+hipError_t launch_gru_series_fwd(const float* xs, long long ldx, int T, int I, const int* series_ptr, int M, int H,
+                                 const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, float* out,
+                                 float* saved, hipStream_t st);
+hipError_t launch_gru_series_bwd(const float* dout, const float* saved, const float* xs, long long ldx, int T, int I,
+                                 const int* series_ptr, int M, int H, const float* w_hh, float* dw_ih, float* db_ih,
+                                 float* dw_hh, float* db_hh, float* work, hipStream_t st);
+hipError_t launch_dom_series_summary(const float* x, long long ldx, int F, int N, const int* series_ptr, int M, int charge_col,
+                                     float* out, long long ldo, hipStream_t st);
 // gemm.hip
 hipError_t launch_gemm_nt(int mode, const Segs& a, int a_lowp, int M, const void* Wp, int Kp, int Npad, int Nreal,
                           const Epi& epi, void* C, long long ldc, int out_lowp, hipStream_t st);

@@ -12,6 +12,8 @@
 //   pct_summary_kernel   one workgroup per (event, summarised column): sort (rank << 32 | value key), NaN last inside its
 //                        cluster, then one thread per (cluster, percentile) does numpy's linear interpolation in fp64.
 //
+//   NodeAsDOMTimeSeries (nodes.py:220-306) is further down, on the same sort routine: dts_rows_kernel, dts_series_kernel.
+//
 // Events of up to PCT_LDS_MAX pulses sort in LDS; larger ones run the same routine on their slice of `work` in global
 // memory (still one workgroup per event, so __syncthreads() orders the steps; correct, not fast).
 #include "launchers.hpp"
@@ -61,6 +63,20 @@ __device__ __forceinline__ int pct_pow2(int n) {
     return P;
 }
 
+// one stable pass: perm[0..n) reordered ascending by the cluster key of column `col`, ties in their present order
+template <typename KP, typename IP>
+__device__ __forceinline__ void pct_sort_pass(KP keys, IP perm, const float* __restrict__ x, long long ldx, int col, int lo, int n,
+                                              int P, int tid) {
+    for (int i = tid; i < P; i += PCT_NT)
+        keys[i] = i < n ? ((u64)pct_cluster_key(x[(long long)(lo + perm[i]) * ldx + col]) << 32) | (unsigned int)i : ~0ull;
+    __syncthreads();
+    pct_sort(keys, P, tid);
+    for (int i = tid; i < n; i += PCT_NT) keys[i] = (u64)(unsigned int)perm[(int)(keys[i] & 0xffffffffu)];
+    __syncthreads();
+    for (int i = tid; i < n; i += PCT_NT) perm[i] = (int)keys[i];
+    __syncthreads();
+}
+
 template <typename KP, typename IP>
 __device__ __forceinline__ void pct_cluster_event(
     KP keys, IP perm, int* part, const float* __restrict__ x, long long ldx, const PctArgs& a, int C, int lo, int n, int tid,
@@ -69,17 +85,7 @@ __device__ __forceinline__ void pct_cluster_event(
     const int P = pct_pow2(n);
     for (int i = tid; i < n; i += PCT_NT) perm[i] = i;
     __syncthreads();
-    for (int c = 0; c < C; ++c) {
-        const int col = a.cl[c];
-        for (int i = tid; i < P; i += PCT_NT)
-            keys[i] = i < n ? ((u64)pct_cluster_key(x[(long long)(lo + perm[i]) * ldx + col]) << 32) | (unsigned int)i : ~0ull;
-        __syncthreads();
-        pct_sort(keys, P, tid);
-        for (int i = tid; i < n; i += PCT_NT) keys[i] = (u64)(unsigned int)perm[(int)(keys[i] & 0xffffffffu)];
-        __syncthreads();
-        for (int i = tid; i < n; i += PCT_NT) perm[i] = (int)keys[i];
-        __syncthreads();
-    }
+    for (int c = 0; c < C; ++c) pct_sort_pass(keys, perm, x, ldx, a.cl[c], lo, n, P, tid);
     // head flags (into keys), then a scan over contiguous chunks
     for (int i = tid; i < n; i += PCT_NT) {
         bool head = i == 0;
@@ -233,6 +239,155 @@ hipError_t launch_percentile_clusters(const float* x, long long ldx, int N, cons
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(pct_summary_kernel, dim3((unsigned)B, (unsigned)S), dim3(PCT_NT), 0, st, x, ldx, a, C, S, P, add_counts, ptr,
                        N, rank, first, start, out_ptr, out, ldo, gkeys);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+//   NodeAsDOMTimeSeries (models/graphs/nodes/nodes.py:220-306): the pulses of an event regrouped into one time series
+//   per DOM.  Row count unchanged; the contract is in include/graphnet_amd.h (gn_dom_time_series).
+//
+//   dts_rows_kernel     one workgroup per event.  Minimum of the time column (NaN if any NaN), C + 1 stable passes (time,
+//                       then the id columns, the first of id_cols first), head flags on the id tuples, a workgroup scan,
+//                       then the permuted rows with the time shifted, the charge raised to 10^x and new_node_col.
+//                       Into `work`: the batch row at which every series of the event starts, and the event's series count.
+//   (launch_scan over the counts -> dom_ptr)
+//   dts_series_kernel   series_ptr[dom_ptr[ev] + r] = start of series r of event ev;  series_ptr[M] = N.
+struct DtsArgs { int id[PCT_CMAX]; };
+
+template <typename KP, typename IP>
+__device__ __forceinline__ void dts_event(
+    KP keys, IP perm, int* part, const float* __restrict__ x, long long ldx, int F, const DtsArgs& a, int C, int time_col,
+    int charge_col, int lo, int n, int tid, float* __restrict__ out, long long ldo, int* __restrict__ start,
+    int* __restrict__ cnt_ev)
+{
+    const int P = pct_pow2(n);
+    // smallest time in the order that puts -0.0 before +0.0; any NaN makes the whole column NaN (numpy's min)
+    unsigned int kmin = 0xffffffffu;
+    int anynan = 0;
+    for (int i = tid; i < n; i += PCT_NT) {
+        const float t = x[(long long)(lo + i) * ldx + time_col];
+        if (t != t) anynan = 1; else kmin = min(kmin, pct_ord(__float_as_uint(t)));
+        perm[i] = i;
+    }
+    part[tid] = (int)kmin;
+    __syncthreads();
+    for (int o = PCT_NT >> 1; o > 0; o >>= 1) {
+        if (tid < o) part[tid] = (int)min((unsigned int)part[tid], (unsigned int)part[tid + o]);
+        __syncthreads();
+    }
+    kmin = (unsigned int)part[0];
+    __syncthreads();
+    part[tid] = anynan;
+    __syncthreads();
+    for (int o = PCT_NT >> 1; o > 0; o >>= 1) {
+        if (tid < o) part[tid] |= part[tid + o];
+        __syncthreads();
+    }
+    anynan = part[0];
+    __syncthreads();
+    const float tmin = anynan ? __builtin_nanf("") : pct_key_value(kmin);
+
+    pct_sort_pass(keys, perm, x, ldx, time_col, lo, n, P, tid);
+    for (int c = 0; c < C; ++c) pct_sort_pass(keys, perm, x, ldx, a.id[c], lo, n, P, tid);
+
+    for (int i = tid; i < n; i += PCT_NT) {                  // head flags (into keys)
+        bool head = i == 0;
+        if (i > 0) {
+            const float* r0 = x + (long long)(lo + perm[i - 1]) * ldx;
+            const float* r1 = x + (long long)(lo + perm[i]) * ldx;
+            for (int c = 0; c < C; ++c) head = head || pct_cluster_key(r0[a.id[c]]) != pct_cluster_key(r1[a.id[c]]);
+        }
+        keys[i] = head ? 1ull : 0ull;
+    }
+    __syncthreads();
+    const int ipt = (n + PCT_NT - 1) / PCT_NT;
+    const int i0 = min(tid * ipt, n), i1 = min(i0 + ipt, n);
+    int mine = 0;
+    for (int i = i0; i < i1; ++i) mine += (int)keys[i];
+    part[tid] = mine;
+    __syncthreads();
+    for (int o = 1; o < PCT_NT; o <<= 1) {                 // inclusive scan of the 256 chunk totals
+        const int v = tid >= o ? part[tid - o] : 0;
+        __syncthreads();
+        part[tid] += v;
+        __syncthreads();
+    }
+    int run = part[tid] - mine;                            // heads before this chunk
+    for (int i = i0; i < i1; ++i)
+        if (keys[i]) start[lo + run++] = lo + i;
+    if (tid == PCT_NT - 1) *cnt_ev = part[tid];
+
+    const int W = F + (charge_col < 0 ? 1 : 0) + 1;
+    for (long long idx = tid; idx < (long long)n * W; idx += PCT_NT) {
+        const int i = (int)(idx / W), c = (int)(idx - (long long)i * W);
+        float v;
+        if (c == W - 1) v = keys[i] ? 1.0f : 0.0f;
+        else if (c >= F) v = 1.0f;                          // no charge column: 10^0
+        else {
+            v = x[(long long)(lo + perm[i]) * ldx + c];
+            if (c == time_col) v = v - tmin;
+            else if (c == charge_col) v = (float)pow(10.0, (double)v);
+        }
+        out[(long long)(lo + i) * ldo + c] = v;
+    }
+}
+
+__global__ __launch_bounds__(PCT_NT) void dts_rows_kernel(
+    const float* __restrict__ x, long long ldx, int F, DtsArgs a, int C, int time_col, int charge_col,
+    const int* __restrict__ ptr, int N, float* __restrict__ out, long long ldo, int* __restrict__ start, int* __restrict__ cnt,
+    u64* __restrict__ gkeys, int* __restrict__ gperm)
+{
+    __shared__ u64 skeys[PCT_LDS_MAX];
+    __shared__ int sperm[PCT_LDS_MAX];
+    __shared__ int part[PCT_NT];
+    const int ev = (int)blockIdx.x, tid = (int)threadIdx.x;
+    const int hi = min(ptr[ev + 1], N), lo = min(max(ptr[ev], 0), hi);
+    const int n = hi - lo;
+    if (n <= 0) { if (tid == 0) cnt[ev] = 0; return; }
+    if (n <= PCT_LDS_MAX)
+        dts_event(skeys, sperm, part, x, ldx, F, a, C, time_col, charge_col, lo, n, tid, out, ldo, start, cnt + ev);
+    else
+        dts_event(gkeys + 2ll * lo, gperm + lo, part, x, ldx, F, a, C, time_col, charge_col, lo, n, tid, out, ldo, start,
+                  cnt + ev);
+}
+
+__global__ __launch_bounds__(PCT_NT) void dts_series_kernel(
+    const int* __restrict__ ptr, int B, int N, const int* __restrict__ start, const int* __restrict__ dom_ptr,
+    int* __restrict__ series_ptr)
+{
+    const int ev = (int)blockIdx.x, tid = (int)threadIdx.x;
+    const int hi = min(ptr[ev + 1], N), lo = min(max(ptr[ev], 0), hi);
+    const int s0 = dom_ptr[ev], ns = min(dom_ptr[ev + 1] - s0, hi - lo);
+    for (int r = tid; r < ns; r += PCT_NT)
+        if (s0 + r < N) series_ptr[s0 + r] = start[lo + r];
+    if (ev == B - 1 && tid == 0) series_ptr[min(max(dom_ptr[B], 0), N)] = N;
+}
+
+// work: [keys 4N + perm N ints, only if N > PCT_LDS_MAX][start N][cnt B][scan tmp]
+long long dom_time_series_work_ints(int B, int N) { return pct_big_ints(N) + (long long)N + B + pct_scan_tmp(B); }
+
+hipError_t launch_dom_time_series(const float* x, long long ldx, int F, int N, const int* ptr, int B, const int* id_cols, int C,
+                                  int time_col, int charge_col, float* out, long long ldo, int* series_ptr, int* dom_ptr,
+                                  int* work, hipStream_t st) {
+    if (B == 0) return series_ptr ? hipMemsetAsync(series_ptr, 0, sizeof(int), st) : hipSuccess;
+    if (N == 0) {
+        hipError_t e = hipMemsetAsync(dom_ptr, 0, sizeof(int) * ((size_t)B + 1), st);
+        return e != hipSuccess ? e : hipMemsetAsync(series_ptr, 0, sizeof(int), st);
+    }
+    DtsArgs a;
+    for (int i = 0; i < PCT_CMAX; ++i) a.id[i] = i < C ? id_cols[i] : 0;
+    u64* gkeys = reinterpret_cast<u64*>(work);              // 8-byte aligned: the first thing in `work`
+    int* gperm = work + 4ll * N;
+    int* start = work + pct_big_ints(N);
+    int* cnt = start + N;
+    int* tmp = cnt + B;
+    hipLaunchKernelGGL(dts_rows_kernel, dim3((unsigned)B), dim3(PCT_NT), 0, st, x, ldx, F, a, C, time_col, charge_col, ptr, N,
+                       out, ldo, start, cnt, gkeys, gperm);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    e = launch_scan(cnt, dom_ptr, B, tmp, dom_ptr + B, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(dts_series_kernel, dim3((unsigned)B), dim3(PCT_NT), 0, st, ptr, B, N, start, dom_ptr, series_ptr);
     return hipGetLastError();
 }
 

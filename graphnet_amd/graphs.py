@@ -1,8 +1,8 @@
 """Graph definitions: ``GraphDefinition`` / ``KNNGraph`` / ``KNNEdges`` / ``MinkowskiKNNEdges`` / ``RadialEdges`` /
-``NodesAsPulses`` / ``PercentileClusters``.
+``NodesAsPulses`` / ``PercentileClusters`` / ``NodeAsDOMTimeSeries``.
 
 Host-side mirror of ``models/graphs/graph_definition.py:148-248``, ``graphs/graphs.py:13-58``,
-``graphs/edges/edges.py:47-117``, ``graphs/edges/minkowski.py:37-99`` and ``graphs/nodes/nodes.py:22-217``.
+``graphs/edges/edges.py:47-117``, ``graphs/edges/minkowski.py:37-99`` and ``graphs/nodes/nodes.py:22-306``.
 
 Difference by design: the reference builds k-NN edges on the CPU, one event
 at a time, inside DataLoader workers.  Here a CPU ``Data`` leaves ``edge_index`` unset and the
@@ -177,6 +177,93 @@ class PercentileClusters(NodeDefinition):
     def _construct_nodes(self, x: torch.Tensor) -> Data:
         ptr = torch.tensor([0, int(x.shape[0])], dtype=torch.int32, device=x.device)
         return Data(x=self.cluster_batch(x, ptr)[0])
+
+
+def dom_time_series_host(x: np.ndarray, id_cols: List[int], time_col: int, charge_col: int = -1) -> np.ndarray:
+    """The contract of ``gn_dom_time_series`` (``include/graphnet_amd.h``) for ONE event in vectorised numpy: fp32
+    ``[n, F]`` -> fp32 ``[n, F + (charge_col < 0) + 1]``.  Bit for bit what the kernel writes, but for the charge column,
+    which is numpy's fp64 ``power`` here."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    n, F = x.shape
+    W = F + (1 if charge_col < 0 else 0) + 1
+    out = np.empty((n, W), dtype=np.float32)
+    if n == 0:
+        return out
+    keys = [_order_keys(x[:, time_col], True)] + [_order_keys(x[:, c], True) for c in id_cols]
+    order = np.lexsort(tuple(keys))                          # stable; the LAST id column most significant, time least
+    t = x[:, time_col]
+    if np.isnan(t).any():
+        tmin = np.float32(np.nan)
+    else:
+        tmin = t.min()
+        if tmin == 0 and np.signbit(t[t == 0]).any():        # -0.0 before +0.0
+            tmin = np.float32(-0.0)
+    out[:, :F] = x[order]
+    with np.errstate(invalid="ignore", over="ignore"):
+        out[:, time_col] = out[:, time_col] - tmin
+        if charge_col < 0:
+            out[:, F] = 1.0
+        else:
+            out[:, charge_col] = np.power(10.0, out[:, charge_col].astype(np.float64)).astype(np.float32)
+    ids = np.stack(keys[1:], axis=1)[order]
+    head = np.ones(n, dtype=bool)
+    head[1:] = (ids[1:] != ids[:-1]).any(axis=1)
+    out[:, W - 1] = head
+    return out
+
+
+class NodeAsDOMTimeSeries(NodeDefinition):
+    """The pulses of an event regrouped into one time series per DOM (``nodes/nodes.py:220-306``; argument names, order
+    and defaults are the reference's): rows grouped by ``id_columns``, ascending in time inside a group, the time shifted
+    to start at 0, the charge raised to ``10^x`` (undoing the detector's ``log10``) and a last column ``new_node_col``
+    that is 1 on every group's first row.  The row count does not change.  The arithmetic is defined operation by
+    operation in ``include/graphnet_amd.h`` (``gn_dom_time_series``).  A device tensor takes one ``gn_dom_time_series``
+    call; a CPU tensor takes :func:`dom_time_series_host`, the same contract in numpy.  On the device a whole batch is
+    regrouped by one call: ``GraphDefinition.batch_from_raw``, whose batch also carries ``series_ptr`` / ``dom_ptr``.
+
+    ``charge_column`` naming no feature (the example's ``"None"``) runs without: a column of ones (``10^0``) is appended
+    before ``new_node_col``, and the output NAMES are still ``input_feature_names + ["new_node_col"]`` as in the reference
+    (``nb_outputs`` counts the names; the matrix is one wider).
+
+    ``max_activations`` is stored and never used, exactly as in the reference (``nodes.py:261``; nothing reads it).
+
+    One definition where the reference has none: its ``argsort`` on time is not stable, so the order among pulses of one
+    DOM with equal times is arbitrary there; here it is the original pulse order.
+    """
+
+    def __init__(self, keys: List[str] = ["dom_x", "dom_y", "dom_z", "dom_time", "charge"],
+                 id_columns: List[str] = ["dom_x", "dom_y", "dom_z"], time_column: str = "dom_time",
+                 charge_column: str = "charge", max_activations: Optional[int] = None) -> None:
+        self._keys = list(keys)
+        super().__init__(input_feature_names=self._keys)
+        self._id_columns = [self._keys.index(key) for key in id_columns]
+        self._time_index = self._keys.index(time_column)
+        self._charge_index: Optional[int] = self._keys.index(charge_column) if charge_column in self._keys else None
+        self._max_activations = max_activations
+
+    def _define_output_feature_names(self, input_feature_names: List[str]) -> List[str]:
+        return input_feature_names + ["new_node_col"]
+
+    def series_batch(self, x: torch.Tensor, ptr: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """``(rows fp32 [N, W], series_ptr int32 [M + 1], dom_ptr int32 [B + 1])`` of the events ``ptr`` marks in ``x``:
+        one device call, or the host path event by event for a CPU tensor."""
+        charge = -1 if self._charge_index is None else self._charge_index
+        if x.is_cuda:
+            from . import ops
+            return ops.dom_time_series(x.to(torch.float32), ptr.to(torch.int32), self._id_columns, self._time_index, charge)
+        xn, bounds = x.detach().to(torch.float32).numpy(), ptr.tolist()
+        parts = [dom_time_series_host(xn[lo:hi], self._id_columns, self._time_index, charge)
+                 for lo, hi in zip(bounds[:-1], bounds[1:])]
+        W = int(x.shape[1]) + (1 if charge < 0 else 0) + 1
+        rows = np.concatenate(parts, axis=0) if parts else np.zeros((0, W), dtype=np.float32)
+        series_ptr = np.append(np.flatnonzero(rows[:, -1]), len(rows)).astype(np.int32)
+        dom_ptr = np.zeros(len(bounds), dtype=np.int32)
+        dom_ptr[1:] = np.cumsum([int(p[:, -1].sum()) for p in parts])
+        return torch.from_numpy(rows), torch.from_numpy(series_ptr), torch.from_numpy(dom_ptr)
+
+    def _construct_nodes(self, x: torch.Tensor) -> Data:
+        ptr = torch.tensor([0, int(x.shape[0])], dtype=torch.int32, device=x.device)
+        return Data(x=self.series_batch(x, ptr)[0])
 
 
 class EdgeDefinition(Model):
@@ -556,6 +643,8 @@ def _batch_from_raw(self: "GraphDefinition", events: "List[np.ndarray]", input_f
     builds the layer-1 k-NN on device, ``gn_knn_graph``).  Events with <= 1 pulse are dropped, as ``collate_fn``
     does.  With a :class:`PercentileClusters` node definition the standardised batch goes through one
     ``gn_percentile_clusters`` call: ``x`` / ``ptr`` / ``batch`` describe the clusters, ``n_pulses`` the raw pulses.
+    With a :class:`NodeAsDOMTimeSeries` node definition it goes through one ``gn_dom_time_series`` call: the rows stay
+    pulses (``x`` / ``ptr`` / ``batch`` / ``n_pulses``), and the batch also carries ``series_ptr`` / ``dom_ptr``.
     ``truth``: name -> per-event sequence (filtered alongside)."""
     from .data import Batch
     keep = [i for i, e in enumerate(events) if len(e) > 1]
@@ -589,9 +678,18 @@ def _batch_from_raw(self: "GraphDefinition", events: "List[np.ndarray]", input_f
         b.ptr = ptr_t.to(device)
         b.n_pulses = n_pulses.to(device)
         b.batch = torch.repeat_interleave(torch.arange(len(keep), dtype=torch.int64), torch.from_numpy(sizes)).to(device)
+    elif isinstance(nd, NodeAsDOMTimeSeries):
+        # one regrouping call over the whole batch: the rows stay pulses, series_ptr / dom_ptr mark the DOM series
+        rows, series_ptr, dom_ptr = nd.series_batch(x, torch.from_numpy(ptr).to(torch.int32).to(x.device))
+        b = Batch(x=rows.type(self.dtype))
+        b.ptr = torch.from_numpy(ptr).to(device)
+        b.n_pulses = n_pulses.to(device)
+        b.batch = torch.repeat_interleave(torch.arange(len(keep), dtype=torch.int64), torch.from_numpy(sizes)).to(device)
+        b.series_ptr = series_ptr
+        b.dom_ptr = dom_ptr
     else:
-        raise NotImplementedError(f"graphnet_amd: batch_from_raw builds NodesAsPulses and PercentileClusters nodes, not "
-                                  f"{nd.__class__.__name__}; use the per-event path")
+        raise NotImplementedError(f"graphnet_amd: batch_from_raw builds NodesAsPulses, PercentileClusters and "
+                                  f"NodeAsDOMTimeSeries nodes, not {nd.__class__.__name__}; use the per-event path")
     ed = self._edge_definition
     if ed is not None and hasattr(ed, "_nb_nearest_neighbours"):
         b.knn_k = int(ed._nb_nearest_neighbours)

@@ -344,6 +344,97 @@ def percentile_clusters(x: Tensor, ptr: Tensor, cluster_cols: Sequence[int], sum
     return out[:M, :W], node_ptr
 
 
+def dom_time_series(x: Tensor, ptr: Tensor, id_cols: Sequence[int], time_col: int, charge_col: int = -1,
+                    out_pitch: Optional[int] = None) -> Tuple[Tensor, Tensor, Tensor]:
+    """Batched DOM time series (``gn_dom_time_series``; the reference's ``NodeAsDOMTimeSeries``,
+    ``graphs/nodes/nodes.py:220-306``): inside each event of ``ptr`` (int32 ``[B + 1]``) the rows of ``x`` (fp32) are
+    grouped by ``id_cols`` and ordered by time inside a group, the time column is shifted to start at 0, the charge column
+    is raised to ``10^x`` (``charge_col = -1``: a column of ones is appended) and ``new_node_col`` marks every group's first
+    row.  Returns ``(rows[N, W], series_ptr int32 [M + 1], dom_ptr int32 [B + 1])``: one call, one read-back (``M``).  The
+    contract is spelled out in ``include/graphnet_amd.h``."""
+    _need(x, torch.float32, "x"); _need(ptr, torch.int32, "ptr")
+    N, F, B = int(x.shape[0]), int(x.shape[1]), int(ptr.shape[0]) - 1
+    C = len(id_cols)
+    W = F + (1 if charge_col < 0 else 0) + 1
+    ldo = W if out_pitch is None else int(out_pitch)
+    if ldo < W:
+        raise ValueError(f"dom_time_series: out_pitch {ldo} < {W} columns")
+    ld = _rows(x, "x") if N > 0 else max(F, 1)
+    idc = (ctypes.c_int32 * max(C, 1))(*[int(v) for v in id_cols])
+    L = _lib.lib()
+    out = torch.empty((N, ldo), dtype=torch.float32, device=x.device)
+    series_ptr = torch.empty(N + 1, dtype=torch.int32, device=x.device)
+    dom_ptr = torch.empty(max(B, 0) + 1, dtype=torch.int32, device=x.device)
+    # int64 elements: the sort keys at the front of `work` are 8 bytes wide
+    work = torch.empty((max(int(L.gn_dom_time_series_work_ints(max(B, 0), N)), 0) + 1) // 2 + 1, dtype=torch.int64, device=x.device)
+    with _timed("dom_time_series"):
+        _lib.check(L.gn_dom_time_series(_p(x), ld, F, N, _p(ptr), B, ctypes.cast(idc, ctypes.c_void_p), C, int(time_col),
+                                        int(charge_col), _p(out), ldo, _p(series_ptr), _p(dom_ptr), _p(work), _st()))
+    if N == 0 or B <= 0:
+        dom_ptr.zero_()
+        return out[:, :W], series_ptr[:1], dom_ptr
+    M = int(dom_ptr[B].item())
+    return out[:, :W], series_ptr[:M + 1], dom_ptr
+
+
+def gru_supported(input_size: int, hidden_size: int) -> bool:
+    return bool(_lib.lib().gn_gru_supported(int(input_size), int(hidden_size)))
+
+
+def gru_series_fwd(xs: Tensor, series_ptr: Tensor, w_ih: Tensor, w_hh: Tensor, b_ih: Tensor, b_hh: Tensor,
+                   save: bool = True) -> Tuple[Tensor, Optional[Tensor]]:
+    """Final hidden state of a GRU over every series of ``xs[T, I]`` (``gn_gru_series_fwd``; series ``s`` = rows
+    ``series_ptr[s] .. series_ptr[s + 1]``): ``(out[M, H], saved)``; fp32 whatever the compute mode.  Raises outside the
+    envelope of ``gn_gru_supported`` - there is no other implementation."""
+    for t, name in ((xs, "xs"), (w_ih, "weight_ih"), (w_hh, "weight_hh"), (b_ih, "bias_ih"), (b_hh, "bias_hh")):
+        _need(t, torch.float32, name)
+    _need(series_ptr, torch.int32, "series_ptr")
+    T, I, M, H = int(xs.shape[0]), int(xs.shape[1]), int(series_ptr.shape[0]) - 1, int(w_hh.shape[1])
+    if tuple(w_ih.shape) != (3 * H, I) or tuple(w_hh.shape) != (3 * H, H):
+        raise ValueError(f"gru_series_fwd: weights {tuple(w_ih.shape)} / {tuple(w_hh.shape)} do not fit xs[:, {I}]")
+    L = _lib.lib()
+    out = torch.empty((M, H), dtype=torch.float32, device=xs.device)
+    saved = torch.empty(max(int(L.gn_gru_saved_floats(T, H)), 4), dtype=torch.float32, device=xs.device) if save else None
+    with _timed("gru_series_fwd"):
+        _lib.check(L.gn_gru_series_fwd(_p(xs), _rows(xs, "xs") if T > 0 else I, T, I, _p(series_ptr), M, H,
+                                       _p(w_ih.contiguous()), _p(w_hh.contiguous()), _p(b_ih.contiguous()),
+                                       _p(b_hh.contiguous()), _p(out), _p(saved), _st()))
+    return out, saved
+
+
+def gru_series_bwd(dout: Tensor, saved: Tensor, xs: Tensor, series_ptr: Tensor, w_hh: Tensor):
+    """``(dW_ih[3H, I], db_ih, dW_hh[3H, H], db_hh)`` of :func:`gru_series_fwd` (``gn_gru_series_bwd``)."""
+    _need(dout, torch.float32, "dout"); _need(saved, torch.float32, "saved"); _need(xs, torch.float32, "xs")
+    T, I, M, H = int(xs.shape[0]), int(xs.shape[1]), int(series_ptr.shape[0]) - 1, int(w_hh.shape[1])
+    L = _lib.lib()
+    dev = xs.device
+    Ip = round_up(I, 4)
+    dw_ih = torch.empty((3 * H, Ip), dtype=torch.float32, device=dev)
+    dw_hh = torch.empty((3 * H, H), dtype=torch.float32, device=dev)
+    db_ih = torch.empty(3 * H, dtype=torch.float32, device=dev)
+    db_hh = torch.empty(3 * H, dtype=torch.float32, device=dev)
+    nwork = int(L.gn_gru_bwd_work_floats(T, I, H))
+    if nwork < 0:
+        raise RuntimeError(f"gru_series_bwd: input size {I} / hidden size {H} outside the envelope of gn_gru_supported")
+    work = torch.empty(max(nwork, 4), dtype=torch.float32, device=dev)
+    with _timed("gru_series_bwd"):
+        _lib.check(L.gn_gru_series_bwd(_p(dout.contiguous()), _p(saved), _p(xs), _rows(xs, "xs") if T > 0 else I, T, I,
+                                       _p(series_ptr), M, H, _p(w_hh.contiguous()), _p(dw_ih), _p(db_ih), _p(dw_hh),
+                                       _p(db_hh), _p(work), _st()))
+    return dw_ih[:, :I], db_ih, dw_hh, db_hh
+
+
+def dom_series_summary(x: Tensor, series_ptr: Tensor, n_cols: int, charge_col: int) -> Tensor:
+    """One row per series (``gn_dom_series_summary``): the series' first row, columns ``[0, n_cols)``, with ``charge_col``
+    replaced by ``asinh`` of the series' summed charge."""
+    _need(x, torch.float32, "x"); _need(series_ptr, torch.int32, "series_ptr")
+    N, M = int(x.shape[0]), int(series_ptr.shape[0]) - 1
+    out = torch.empty((M, n_cols), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().gn_dom_series_summary(_p(x), _rows(x, "x") if N > 0 else int(x.shape[1]), int(n_cols), N,
+                                                _p(series_ptr), M, int(charge_col), _p(out), max(n_cols, 1), _st()))
+    return out
+
+
 def table_from_edge_index(edge_index: Tensor, N: int, K: int) -> NeighbourTable:
     """Loader-supplied ``edge_index`` -> neighbour table.  PyG's ``EdgeConv`` takes edges in any order and of any
     in-degree, so this does too: edges that are not grouped by ascending target are stable-sorted by target first,
@@ -413,6 +504,15 @@ def standardize(x: Tensor, programs: Sequence[Sequence[Tuple[str, float]]]) -> T
 def graph_globals(x: Tensor, ptr: Tensor, g: NeighbourTable, n_pulses: Tensor) -> Tensor:
     _need(x, torch.float32, "x"); _need(n_pulses, torch.int32, "n_pulses")
     B, F = int(ptr.shape[0]) - 1, int(x.shape[1])
+    if F > 32:
+        # the kernel sums up to 32 columns (RNN_TITO feeds 69): column blocks of 32, the last one moved left so that it
+        # is full.  A column's mean does not depend on its block; the homophily and log10(n) columns come from block 0.
+        first = graph_globals(x[:, :32], ptr, g, n_pulses)
+        means = [first[:, :32]]
+        for c0 in range(32, F, 32):
+            lo = min(c0, F - 32)
+            means.append(graph_globals(x[:, lo:lo + 32], ptr, g, n_pulses)[:, c0 - lo:32])
+        return torch.cat(means + [first[:, 32:]], dim=1)
     out = torch.empty((B, F + 5), dtype=torch.float32, device=x.device)
     N = int(x.shape[0])
     scratch = _event_scratch(B, N, 0, x.device)         # a few huge events: one workgroup per event slice

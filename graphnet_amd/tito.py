@@ -212,6 +212,23 @@ class _DynTransFunction(torch.autograd.Function):
         return (None, dx) + tuple(grads)
 
 
+class _GlobalsFunction(torch.autograd.Function):
+    """``ops.graph_globals`` for node features that carry a gradient (``RNN_TITO``: the GRU states are columns of ``x``):
+    the per-event feature means pass it on (``dynedge_kaggle_tito.py:214-234``: ``scatter_mean`` is differentiable); the
+    homophily columns compare for equality and ``log10(n_pulses)`` is data."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, ptr: Tensor, batch: Tensor, table: Any, n_pulses: Tensor) -> Tensor:  # type: ignore[override]
+        ctx.ptr, ctx.batch, ctx.shape = ptr, batch, (int(x.shape[0]), int(x.shape[1]))
+        return ops.graph_globals(x, ptr, table, n_pulses)
+
+    @staticmethod
+    def backward(ctx, gout: Tensor):  # type: ignore[override]
+        N, F = ctx.shape
+        dx = ops.segment_pool_bwd(gout[:, :F].to(torch.float32), F, ctx.ptr, ctx.batch, N, ["mean"], None, None, None)
+        return dx, None, None, None, None
+
+
 class _PostPoolFunction(torch.autograd.Function):
     """Post-processing MLP (Linear + LeakyReLU per layer, ``dynedge_kaggle_tito.py:160-174``) followed by the
     global pooling (``l.198-212``).  ``params``: W, b per layer."""
@@ -405,7 +422,10 @@ class DynEdgeTITO(GNN):
             table = ops.table_from_edge_index(ei, N, self._nb_neighbours) if ei is not None else \
                 ops.knn_graph(x, self._graph_columns, batch32, ptr32, self._nb_neighbours, strict=self._knn_strict)
         plan = ops.attention_plan(ptr32)
-        gv = ops.graph_globals(x, ptr32, table, n_pulses) if self._use_global_features else None
+        if self._use_global_features and x.requires_grad:
+            gv = _GlobalsFunction.apply(x, ptr32, batch32, table, n_pulses)
+        else:
+            gv = ops.graph_globals(x, ptr32, table, n_pulses) if self._use_global_features else None
         seed_log: List[List[int]] = []
         # static graph: one table without overflow rows for the fused EdgeConvTito kernels (bf16 mode), shared by all
         # DynTrans layers; its reverse lists are built once

@@ -107,6 +107,58 @@ int gn_percentile_clusters(const float* x, int64_t ldx, int32_t N, const int32_t
                            const double* q_host, int32_t P, int32_t add_counts,
                            float* out, int64_t ldo, int32_t* out_ptr, int32_t* work, void* stream);
 
+/* NodeAsDOMTimeSeries (models/graphs/nodes/nodes.py:220-306): the pulses of each event regrouped into one time series per
+ * DOM; the row count does not change.  x[N, ldx] with F feature columns, fp32 in and out, out must not overlap x; ptr[B+1]
+ * with ptr[0] = 0 and ptr[B] = N.  Per event:
+ *   row order: ONE stable sort of the event's rows.  Keys, most significant first: the id columns in np.lexsort order (the
+ *     LAST of id_cols most significant), then the time column ascending, then the original pulse index.  Id keys are those of
+ *     gn_percentile_clusters (-0.0 taken as +0.0, every NaN one value after +inf); the time key likewise takes -0.0 as +0.0
+ *     and puts NaN last, as argsort does.  (The reference runs an unstable argsort on time and then a stable lexsort: the
+ *     order among equal times of one DOM is a definition of this library.)  Done as C + 1 stable passes, time first.
+ *   time column: x - tmin, one fp32 subtraction; tmin = the event's smallest time (-0.0 before +0.0), or NaN if any time of
+ *     the event is NaN (numpy's min propagates it), which makes the whole column NaN.
+ *   charge column: (float) pow(10.0, (double) v), undoing the detector's log10.  charge_col = -1: no such column; a column
+ *     of exactly 1.0f is appended at index F (the reference inserts zeros and raises 10 to them).
+ *   last column, new_node_col: 1.0f on the first row of every id tuple of the event, 0.0f elsewhere.
+ *   W = F + (charge_col < 0) + 1 columns; every other column is copied bit for bit.
+ * series_ptr, int32 with room for N + 1: the batch row at which each of the M series starts, then N.  dom_ptr[B+1]: series
+ * offsets per event, dom_ptr[B] = M.  An empty batch writes series_ptr[0] = 0; empty events are legal.
+ * id_cols: HOST int[C], 1 <= C <= 8; id, time and charge columns distinct and < F <= ldx; ldo >= W; N <= 2^28.
+ * work: gn_dom_time_series_work_ints(B, N) ints, 8-byte aligned.  Events of up to gn_percentile_lds_max() pulses sort in
+ * LDS, larger ones in `work` (correct, not fast). */
+int64_t gn_dom_time_series_work_ints(int32_t B, int32_t N);
+int gn_dom_time_series(const float* x, int64_t ldx, int32_t F, int32_t N, const int32_t* ptr, int32_t B,
+                       const int32_t* id_cols_host, int32_t C, int32_t time_col, int32_t charge_col,
+                       float* out, int64_t ldo, int32_t* series_ptr, int32_t* dom_ptr, int32_t* work, void* stream);
+
+/* Ragged GRU recurrence over series (models/rnn/node_rnn.py:105-111; layer 0 of torch.nn.GRU).  Series s owns rows
+ * series_ptr[s] .. series_ptr[s+1] of xs[T, ldx] (I columns); series_ptr[0] = 0, series_ptr[M] = T, no empty series.  Gate
+ * order and tensors are torch.nn.GRU's: r, z, n; weight_ih[3H, I], weight_hh[3H, H], bias_ih[3H], bias_hh[3H], contiguous.
+ * h = 0, then for every row t of the series
+ *   gi = W_ih x_t + b_ih;  gh = W_hh h + b_hh;  r = sigmoid(gi_r + gh_r);  z = sigmoid(gi_z + gh_z);
+ *   n = tanh(gi_n + r * gh_n);  h = (1 - z) * n + z * h
+ * and out[s, 0..H) = h after the last row.  fp32 whatever the compute mode of the other entries; sums in a fixed order, no
+ * float atomics: two runs on one input agree bit for bit.
+ * Envelope (gn_gru_supported(I, H) == 1): 1 <= I <= 32, 4 <= H <= 64, H a multiple of 4.  Outside it the entries fail.
+ * saved (null for inference): gn_gru_saved_floats(T, H) = 5*T*H floats, 16-byte aligned: planes [T, H] of r, z, n, gh_n and
+ * h_prev (zeros on a series' first row).
+ * gn_gru_series_bwd: dout[M, H] -> dw_ih[3H, Ip] (Ip = I rounded up to a multiple of 4; the padding columns are 0),
+ * db_ih[3H], dw_hh[3H, H], db_hh[3H], overwritten.  xs gets no gradient.  work: gn_gru_bwd_work_floats(T, I, H) floats,
+ * 16-byte aligned (the per-row pre-activation gradients and the split-reduction slabs of the four sums). */
+int32_t gn_gru_supported(int32_t I, int32_t H);
+int64_t gn_gru_saved_floats(int32_t T, int32_t H);
+int64_t gn_gru_bwd_work_floats(int32_t T, int32_t I, int32_t H);
+int gn_gru_series_fwd(const float* xs, int64_t ldx, int32_t T, int32_t I, const int32_t* series_ptr, int32_t M, int32_t H,
+                      const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
+                      float* out, float* saved, void* stream);
+int gn_gru_series_bwd(const float* dout, const float* saved, const float* xs, int64_t ldx, int32_t T, int32_t I,
+                      const int32_t* series_ptr, int32_t M, int32_t H, const float* w_hh,
+                      float* dw_ih, float* db_ih, float* dw_hh, float* db_hh, float* work, void* stream);
+/* One row per series (node_rnn.py:113-122): out[s, 0..F) = x[series_ptr[s], 0..F), but column charge_col =
+ * asinhf((5 * sum) / 5), sum = the fp32 sum of x[t, charge_col] over the series' rows in row order. */
+int gn_dom_series_summary(const float* x, int64_t ldx, int32_t F, int32_t N, const int32_t* series_ptr, int32_t M,
+                          int32_t charge_col, float* out, int64_t ldo, void* stream);
+
 /* exclusive scan; tmp: >= gn_scan_tmp_ints(n) ints; total (optional) receives the sum */
 int64_t gn_scan_tmp_ints(int64_t n);
 int gn_scan_i32(const int32_t* in, int32_t* out, int32_t n, int32_t* tmp, int32_t* total, void* stream);
