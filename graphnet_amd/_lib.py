@@ -104,6 +104,10 @@ SIGNATURES = {
     "gn_attention_bwd": (I32, [I32, P, I64, I32, I32, P, P, I32, I32, P, I64, P, I64, P, P, P, I64, U32, U32, P]),
     "gn_attention_fwd_bits": (I32, [P, I64, I32, I32, P, P, I32, I32, P, I64, P, U32, U32, P, P, P, I64, P]),
     "gn_attention_bwd_bits": (I32, [P, I64, I32, I32, P, P, I32, I32, P, I64, P, I64, P, P, P, I64, U32, P, P, P, I64, P]),
+    "gn_rel_attention_supported": (I32, [I32]),
+    "gn_rel_attention_fwd": (I32, [P, I64, P, I64, P, I64, P, I32, I32, P, P, I32, I32, P, I64, P, I64, P, P]),
+    "gn_rel_attention_bwd": (I32, [P, I64, P, I64, P, I64, P, I32, I32, P, P, I32, I32, P, I64, P, I64, P, I64, P, I64, P, P,
+                                   P, I64, P, I64, P]),
     "gn_bn_blocks": (I64, [I64]),
     "gn_bn_sums": (I32, [I32, I32, P, I64, I64, I32, P, P, I64, P, P, P, P, P, P, P]),
     "gn_bn_finalize": (I32, [P, P, I32, c_float, P, P, P, P]),

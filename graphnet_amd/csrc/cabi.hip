@@ -619,6 +619,35 @@ int gn_attention_bwd_bits(const void* qkv, int64_t ld, int32_t H, int32_t DH, co
     return fail(r, "gn_attention_bwd_bits");
 }
 
+int gn_rel_attention_supported(int32_t DH) { return gn::rel_attn_supported(DH) ? 1 : 0; }
+int gn_rel_attention_fwd(const float* qkv, int64_t ld, const float* qp, int64_t ldqp, const float* xt, int64_t ldxt,
+                         const float* freq, int32_t H, int32_t DH, const int32_t* ptr, const int32_t* tile_ptr, int32_t B,
+                         int32_t N, float* out, int64_t ldo, float* u, int64_t ldu, float* lse2, void* stream) {
+    if (H <= 0 || B < 0 || N < 0) return bad("gn_rel_attention_fwd", "H > 0, B >= 0, N >= 0");
+    if (N > 0 && B > 0 && (!qkv || !qp || !xt || !freq || !ptr || !tile_ptr || !out || !u || !lse2))
+        return bad("gn_rel_attention_fwd", "null pointer");
+    hipError_t r = gn::launch_rel_attn_fwd(qkv, ld, qp, ldqp, xt, ldxt, freq, H, DH, ptr, tile_ptr, B, N, out, ldo, u, ldu, lse2,
+                                           S(stream));
+    if (r == hipErrorInvalidValue)
+        return bad("gn_rel_attention_fwd", "head width 32, row pitches multiples of 16 bytes and at least the row width, xt pitch >= 4");
+    return fail(r, "gn_rel_attention_fwd");
+}
+int gn_rel_attention_bwd(const float* qkv, int64_t ld, const float* qp, int64_t ldqp, const float* xt, int64_t ldxt,
+                         const float* freq, int32_t H, int32_t DH, const int32_t* ptr, const int32_t* tile_ptr, int32_t B,
+                         int32_t N, const float* out, int64_t ldo, const float* u, int64_t ldu, const float* dout,
+                         int64_t lddo, const float* du, int64_t lddu, const float* lse2, float* delta, float* dqkv,
+                         int64_t lddq, float* dqp, int64_t lddqp, void* stream) {
+    if (H <= 0 || B < 0 || N < 0) return bad("gn_rel_attention_bwd", "H > 0, B >= 0, N >= 0");
+    if (N > 0 && B > 0 && (!qkv || !qp || !xt || !freq || !ptr || !tile_ptr || !out || !u || !dout || !du || !lse2 || !delta ||
+                           !dqkv || !dqp))
+        return bad("gn_rel_attention_bwd", "null pointer");
+    hipError_t r = gn::launch_rel_attn_bwd(qkv, ld, qp, ldqp, xt, ldxt, freq, H, DH, ptr, tile_ptr, B, N, out, ldo, u, ldu, dout,
+                                           lddo, du, lddu, lse2, delta, dqkv, lddq, dqp, lddqp, S(stream));
+    if (r == hipErrorInvalidValue)
+        return bad("gn_rel_attention_bwd", "head width 32, row pitches multiples of 16 bytes and at least the row width, xt pitch >= 4");
+    return fail(r, "gn_rel_attention_bwd");
+}
+
 int gn_dropout(const void* x, int64_t ldx, int32_t x_lowp, const float* res, int64_t ldres, void* y, int64_t ldy,
                int32_t y_lowp, int64_t rows, int32_t cols, uint32_t seed, uint32_t thresh, void* stream) {
     hipError_t r = gn::launch_dropout(x, ldx, x_lowp, res, ldres, y, ldy, y_lowp, rows, cols, seed, thresh, S(stream));

@@ -171,6 +171,16 @@ hipError_t launch_attn_bwd(int lowp, const void* qkv, long long ld, int H, int D
                            const float* lse2, float* delta, void* dqkv, long long lddq, unsigned seed, unsigned thresh,
                            const unsigned int* bits_r, const unsigned int* bits_c, const long long* evoff, long long plane,
                            hipStream_t st);
+// attn_rel.hip: ragged attention with the spacetime bias of DeepIce recomputed per pair (fp32, head width 32)
+bool rel_attn_supported(int DH);
+hipError_t launch_rel_attn_fwd(const float* qkv, long long ld, const float* qp, long long ldqp, const float* xt, long long ldxt,
+                               const float* freq, int H, int DH, const int* ptr, const int* tile_ptr, int B, int N,
+                               float* out, long long ldo, float* u, long long ldu, float* lse2, hipStream_t st);
+hipError_t launch_rel_attn_bwd(const float* qkv, long long ld, const float* qp, long long ldqp, const float* xt, long long ldxt,
+                               const float* freq, int H, int DH, const int* ptr, const int* tile_ptr, int B, int N,
+                               const float* out, long long ldo, const float* u, long long ldu, const float* dout,
+                               long long lddo, const float* du, long long lddu, const float* lse2, float* delta,
+                               float* dqkv, long long lddq, float* dqp, long long lddqp, hipStream_t st);
 // generic.hip: dropout (+ residual add); thresh = round(p * 2^32)
 hipError_t launch_dropout(const void* x, long long ldx, int x_lowp, const float* res, long long ldres, void* y, long long ldy,
                           int y_lowp, long long rows, int cols, unsigned seed, unsigned thresh, hipStream_t st);

@@ -134,6 +134,22 @@ class IceCube86(Detector):
         }
 
 
+class IceCubeKaggle(Detector):
+    """`Detector` class of the Kaggle competition data (``icecube.py:51-80``): the ``icecube86`` geometry table."""
+
+    xyz = ["x", "y", "z"]
+    geometry_table_file = ("icecube", "icecube86.parquet")
+    string_id_column = "string"
+    sensor_id_column = "sensor_id"
+
+    def feature_ops(self):
+        xyz = [("div", 500.0)]
+        return {
+            "x": xyz, "y": xyz, "z": xyz,
+            "time": [("sub", 1.0e04), ("div", 3.0e4)], "charge": [("log10", 0.0), ("div", 3.0)], "auxiliary": [],
+        }
+
+
 class IceCubeDeepCore(IceCube86):
     def feature_ops(self):
         return {

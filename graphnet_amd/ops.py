@@ -1264,3 +1264,65 @@ def attention_bwd(qkv: Tensor, n_head: int, ptr: Tensor, plan: Tensor, out: Tens
                                                _rows(dout, "dout"), _p(lse2), _p(delta), _p(dqkv), d3,
                                                (drop[0] & 0xFFFFFFFF) if drop else 0, drop[1] if drop else 0, _st()))
     return dqkv
+
+
+# ------------------------------------------------------------------------------ ragged attention + spacetime bias (DeepIce)
+def rel_attention_supported(dh: int) -> bool:
+    """Head widths of the biased attention kernels (``gn_rel_attention_supported``)."""
+    return bool(_lib.lib().gn_rel_attention_supported(int(dh)))
+
+
+def rel_attention_freq(dh: int, device) -> Tensor:
+    """The ``dh / 2`` frequencies of ``SinusoidalPosEmb(dh)``: the fp32 operations of ``rnn.sinusoidal_pos_emb``, on the host."""
+    half_dim = dh / 2
+    emb = torch.log(torch.tensor([10000.0], dtype=torch.float32)) / half_dim
+    return torch.exp(torch.arange(half_dim) * (-emb)).to(device)
+
+
+def _rel_check(qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int) -> Tuple[int, int]:
+    for t, name in ((qkv, "qkv"), (qp, "qp"), (xt, "xt"), (freq, "freq")):
+        _need(t, torch.float32, name)
+    N, d = int(qp.shape[0]), int(qp.shape[1])
+    if int(qkv.shape[0]) != N or int(qkv.shape[1]) != 3 * d or d % n_head or int(xt.shape[0]) != N or int(xt.shape[1]) < 4:
+        raise ValueError("need qkv [N, 3*d], qp [N, d] with d a multiple of the number of heads, xt [N, >= 4]")
+    dh = d // n_head
+    if not rel_attention_supported(dh):
+        raise NotImplementedError(f"biased ragged attention: head width {dh} is not built (32 is); no fallback")
+    if int(freq.numel()) != dh // 2 or not freq.is_contiguous():
+        raise ValueError("freq must hold dh / 2 contiguous frequencies")
+    return N, d
+
+
+def rel_attention_fwd(qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, ptr: Tensor, plan: Tensor):
+    """Ragged attention with the spacetime bias of ``DeepIce`` recomputed per pair (``gn_rel_attention_fwd``): scores
+    ``q k / sqrt(dh) + qp . s_ij``, ``s_ij`` the sinusoidal embedding of the clipped 4-distance of pulses ``i``, ``j`` (columns
+    0-3 of ``xt``: x, y, z, time).  fp32.  -> (out ``[N, d]`` = sum_j a_ij v_j, u ``[N, d]`` = sum_j a_ij s_ij, lse2 ``[N, H]``)."""
+    N, d = _rel_check(qkv, qp, xt, freq, n_head)
+    B = int(ptr.shape[0]) - 1
+    out = torch.empty((N, d), dtype=torch.float32, device=qkv.device)
+    u = torch.empty((N, d), dtype=torch.float32, device=qkv.device)
+    lse2 = torch.empty((N, n_head), dtype=torch.float32, device=qkv.device)
+    with _timed("rel_attention_fwd"):
+        _lib.check(_lib.lib().gn_rel_attention_fwd(_p(qkv), _rows(qkv, "qkv"), _p(qp), _rows(qp, "qp"), _p(xt), _rows(xt, "xt"),
+                                                   _p(freq), n_head, d // n_head, _p(ptr), _p(plan), B, N, _p(out), d, _p(u), d,
+                                                   _p(lse2), _st()))
+    return out, u, lse2
+
+
+def rel_attention_bwd(qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, ptr: Tensor, plan: Tensor,
+                      out: Tensor, u: Tensor, lse2: Tensor, dout: Tensor, du: Tensor) -> Tuple[Tensor, Tensor]:
+    """Gradients of :func:`rel_attention_fwd` -> (dqkv ``[N, 3 d]``, dqp ``[N, d]``); ``xt`` carries none."""
+    N, d = _rel_check(qkv, qp, xt, freq, n_head)
+    for t, name in ((out, "out"), (u, "u"), (dout, "dout"), (du, "du"), (lse2, "lse2")):
+        _need(t, torch.float32, name)
+    B = int(ptr.shape[0]) - 1
+    dqkv = torch.empty((N, 3 * d), dtype=torch.float32, device=qkv.device)
+    dqp = torch.empty((N, d), dtype=torch.float32, device=qkv.device)
+    delta = torch.empty((N, n_head), dtype=torch.float32, device=qkv.device)
+    with _timed("rel_attention_bwd"):
+        _lib.check(_lib.lib().gn_rel_attention_bwd(_p(qkv), _rows(qkv, "qkv"), _p(qp), _rows(qp, "qp"), _p(xt), _rows(xt, "xt"),
+                                                   _p(freq), n_head, d // n_head, _p(ptr), _p(plan), B, N, _p(out),
+                                                   _rows(out, "out"), _p(u), _rows(u, "u"), _p(dout), _rows(dout, "dout"),
+                                                   _p(du), _rows(du, "du"), _p(lse2), _p(delta), _p(dqkv), 3 * d, _p(dqp), d,
+                                                   _st()))
+    return dqkv, dqp

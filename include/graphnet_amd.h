@@ -481,6 +481,31 @@ int gn_segment_pool_bwd(const float* gout, int32_t C, const int32_t* ptr, const 
                         const float* gate, int64_t ldgate, void* dx, int64_t lddx, int32_t dx_lowp, void* stream);
 /* (dx: fp32, or bf16 when dx_lowp) */
 
+/* ---- ragged attention with the spacetime bias of DeepIce (models/components/layers.py:389-499, embedding.py:139-175) ---- */
+/* Attention_rel without the [B, L, L, dh] bias tensor.  With s_ij the sinusoidal embedding (width DH) of the clipped
+ * 4-distance of pulses i, j of one event and R_ij = W s_ij + b its projection, the reference's scores and outputs are
+ *   q~_ih . k_jh + q~_ih . R_ij = q~_ih . k_jh + (W^T q~_ih) . s_ij + const_j,   sum_j a_ihj (v_jh + R_ij) = O_ih + W U_ih + b,
+ * q~ = q / sqrt(DH), U_ih = sum_j a_ihj s_ij.  These entries take qkv[N, ld] = [Q | K | V] (each H*DH wide), the per-row
+ * operand qp[N, ldqp] = W^T q~ per head (H*DH wide; the 1/sqrt(DH) is ALREADY in it), xt[N, ldxt] (columns 0-2 position,
+ * column 3 time, ldxt >= 4) and freq[DH/2] (the frequencies of SinusoidalPosEmb(DH), formed on the host), recompute s_ij
+ * per pair and return out = O, u = U (both [N, H*DH]) and lse2[N, H] = log2 of the softmax denominators.  W and b are
+ * applied by the caller.  All tensors fp32; DH = 32 (gn_rel_attention_supported); ptr / tile_ptr as gn_attention_fwd
+ * (the plan of gn_attention_plan); row pitches multiples of 4 floats.  No atomics: two runs agree bit for bit.
+ * CONTRACT of the pair argument, fp32, every operation rounded on its own (no fused multiply-add), differences query - key:
+ *   ds = ((dx*dx + dy*dy) + dz*dz) - (dt*18)*(dt*18),  d = sign(ds) * sqrt(|ds|),  a = 1024 * min(max(d, -4), 4),
+ *   s_ij = [sin(a * freq[k]) | cos(a * freq[k])], k < DH/2, the products a * freq[k] and the sines to ~1e-6 absolute.
+ * gn_rel_attention_bwd: given dout, du (gradients w.r.t. out, u) and the forward's out, u, lse2 -> dqkv[N, lddq]
+ * (3*H*DH wide) and dqp[N, lddqp]; xt and freq get no gradient; delta[N, H] fp32 is scratch. */
+int gn_rel_attention_supported(int32_t DH);
+int gn_rel_attention_fwd(const float* qkv, int64_t ld, const float* qp, int64_t ldqp, const float* xt, int64_t ldxt,
+                         const float* freq, int32_t H, int32_t DH, const int32_t* ptr, const int32_t* tile_ptr, int32_t B,
+                         int32_t N, float* out, int64_t ldo, float* u, int64_t ldu, float* lse2, void* stream);
+int gn_rel_attention_bwd(const float* qkv, int64_t ld, const float* qp, int64_t ldqp, const float* xt, int64_t ldxt,
+                         const float* freq, int32_t H, int32_t DH, const int32_t* ptr, const int32_t* tile_ptr, int32_t B,
+                         int32_t N, const float* out, int64_t ldo, const float* u, int64_t ldu, const float* dout,
+                         int64_t lddo, const float* du, int64_t lddu, const float* lse2, float* delta, float* dqkv,
+                         int64_t lddq, float* dqp, int64_t lddqp, void* stream);
+
 /* ---- ragged multi-head self attention (DynTrans, models/components/layers.py:166-197) ---- */
 /* Replaces to_dense_batch + torch.nn.TransformerEncoder's attention + x[mask]: every pulse attends to the
  * pulses of its own event (ptr), nothing is padded.  qkv[N, ld] = [Q | K | V], each H*DH wide (the in_proj
