@@ -11,7 +11,8 @@ from .detector import (  # noqa: F401
 )
 from .model import Model, ModelConfig  # noqa: F401
 from .graphs import (  # noqa: F401
-    GraphDefinition, KNNEdges, KNNGraph, MinkowskiKNNEdges, NodeAsDOMTimeSeries, NodesAsPulses, PercentileClusters, RadialEdges,
+    GraphDefinition, IceMixNodes, KNNEdges, KNNGraph, MinkowskiKNNEdges, NodeAsDOMTimeSeries, NodesAsPulses, PercentileClusters,
+    RadialEdges,
 )
 from .gnn import GNN, DynEdge, DynEdgeConv, DynEdgeJINST  # noqa: F401
 from .tito import DynEdgeTITO, DynTrans  # noqa: F401

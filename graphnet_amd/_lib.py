@@ -37,6 +37,7 @@ SIGNATURES = {
     "gn_percentile_clusters": (I32, [P, I64, I32, P, I32, P, I32, P, I32, P, I32, I32, P, I64, P, P, P]),
     "gn_dom_time_series_work_ints": (I64, [I32, I32]),
     "gn_dom_time_series": (I32, [P, I64, I32, I32, P, I32, P, I32, I32, I32, P, I64, P, P, P, P]),
+    "gn_icemix_nodes": (I32, [P, I64, I32, I32, P, I32, I32, I32, I32, P, I32, U32, P, I32, P, I64, P, P, P]),
     "gn_gru_supported": (I32, [I32, I32]),
     "gn_gru_saved_floats": (I64, [I32, I32]),
     "gn_gru_bwd_work_floats": (I64, [I32, I32, I32]),

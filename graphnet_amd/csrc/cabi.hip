@@ -143,6 +143,23 @@ int gn_dom_time_series(const float* x, int64_t ldx, int32_t F, int32_t N, const 
                                            dom_ptr, work, S(stream)), me);
 }
 
+int gn_icemix_nodes(const float* x, int64_t ldx, int32_t F, int32_t N, const int32_t* ptr, int32_t B, int32_t max_pulses,
+                    int32_t hlc_col, int32_t z_col, const double* table, int32_t T, uint32_t seed, const uint32_t* event_ids,
+                    int32_t key_bits, float* out, int64_t ldo, int32_t* out_ptr, int32_t* ids, void* stream) {
+    const char* me = "gn_icemix_nodes";
+    if (N < 0 || B < 0 || N > (1 << 28)) return bad(me, "need B >= 0 and 0 <= N <= 2^28");
+    if (F < 1 || F > ldx) return bad(me, "need 1 <= F <= ldx");
+    if (max_pulses < 1) return bad(me, "need max_pulses >= 1");
+    if (key_bits < 1 || key_bits > 32) return bad(me, "need 1 <= key_bits <= 32");
+    if (hlc_col < -1 || hlc_col >= F || z_col < -1 || z_col >= F) return bad(me, "hlc / z column out of range (-1: none)");
+    if (z_col >= 0 && (T < 2 || T > 1024 || !table)) return bad(me, "ice columns need table[3*T], 2 <= T <= 1024");
+    if (ldo < (int64_t)F + (z_col >= 0 ? 2 : 0)) return bad(me, "need ldo >= F + 2*(z_col >= 0)");
+    if (B > 0 && (!ptr || !out_ptr)) return bad(me, "need ptr[B+1] and out_ptr[B+1]");
+    if (N > 0 && B > 0 && (!x || !out || !ids)) return bad(me, "need x, out[M, ldo] and ids[M]");
+    return fail(gn::launch_icemix_nodes(x, ldx, F, N, ptr, B, max_pulses, hlc_col, z_col, table, T, seed, event_ids, key_bits,
+                                        out, ldo, out_ptr, ids, S(stream)), me);
+}
+
 int32_t gn_gru_supported(int32_t I, int32_t H) { return gn::gru_supported(I, H); }
 int64_t gn_gru_saved_floats(int32_t T, int32_t H) { return (T < 0 || H < 1) ? -1 : gn::gru_saved_floats(T, H); }
 int64_t gn_gru_bwd_work_floats(int32_t T, int32_t I, int32_t H) {

@@ -48,6 +48,9 @@ long long dom_time_series_work_ints(int B, int N);
 hipError_t launch_dom_time_series(const float* x, long long ldx, int F, int N, const int* ptr, int B, const int* id_cols, int C,
                                   int time_col, int charge_col, float* out, long long ldo, int* series_ptr, int* dom_ptr,
                                   int* work, hipStream_t st);
+hipError_t launch_icemix_nodes(const float* x, long long ldx, int F, int N, const int* ptr, int B, int L, int hlc_col, int z_col,
+                               const double* table, int T, unsigned int seed, const unsigned int* event_ids, int key_bits,
+                               float* out, long long ldo, int* out_ptr, int* ids, hipStream_t st);
 // rnn.hip
 int gru_supported(int I, int H);
 long long gru_saved_floats(int T, int H);

@@ -13,6 +13,7 @@
 //                        cluster, then one thread per (cluster, percentile) does numpy's linear interpolation in fp64.
 //
 //   NodeAsDOMTimeSeries (nodes.py:220-306) is further down, on the same sort routine: dts_rows_kernel, dts_series_kernel.
+//   IceMixNodes (nodes.py:309-453) is last and sorts nothing: imx_ptr_kernel, imx_nodes_kernel.
 //
 // Events of up to PCT_LDS_MAX pulses sort in LDS; larger ones run the same routine on their slice of `work` in global
 // memory (still one workgroup per event, so __syncthreads() orders the steps; correct, not fast).
@@ -388,6 +389,174 @@ hipError_t launch_dom_time_series(const float* x, long long ldx, int F, int N, c
     e = launch_scan(cnt, dom_ptr, B, tmp, dom_ptr + B, st);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(dts_series_kernel, dim3((unsigned)B), dim3(PCT_NT), 0, st, ptr, B, N, start, dom_ptr, series_ptr);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+//   IceMixNodes (models/graphs/nodes/nodes.py:309-453): every event cut to a uniformly random L of its pulses, kept in
+//   pulse order, the hlc column flipped and two ice columns interpolated from a table.  The contract is in
+//   include/graphnet_amd.h (gn_icemix_nodes).  No scratch in global memory, no limit on the size of an event.
+//
+//   imx_ptr_kernel      one workgroup: out_ptr = exclusive scan of min(n_b, L), straight from ptr (launch_scan would need
+//                       a count array and its tmp, which this entry does not have).
+//   imx_nodes_kernel    one workgroup per event.  n <= L: a coalesced row copy.  n > L: a radix select on the stateless
+//                       hash (four passes of 8-bit digits over a 256-bin integer histogram, the hash recomputed each time)
+//                       gives the L-th smallest key t and the number r of pulses with key t to keep; one pass in index
+//                       order (chunks of 256, a workgroup scan of packed (below, equal) counts) ranks the kept pulses and
+//                       writes ids; then the same row copy through ids.
+constexpr int IMX_PT = 1024;
+static_assert(PCT_NT == 256, "imx_nodes_kernel: one thread per histogram bin");
+
+// inclusive scan of part[0..NT) in place; ends with a barrier
+template <int NT>
+__device__ __forceinline__ void imx_scan(int* part, int tid) {
+    for (int o = 1; o < NT; o <<= 1) {
+        const int v = tid >= o ? part[tid - o] : 0;
+        __syncthreads();
+        part[tid] += v;
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(IMX_PT) void imx_ptr_kernel(const int* __restrict__ ptr, int B, int N, int L,
+                                                         int* __restrict__ out_ptr)
+{
+    __shared__ int part[IMX_PT];
+    const int tid = (int)threadIdx.x;
+    int run = 0;
+    for (int base = 0; base < B; base += IMX_PT) {
+        const int b = base + tid;
+        int c = 0;
+        if (b < B) {
+            const int hi = min(ptr[b + 1], N), lo = min(max(ptr[b], 0), hi);
+            c = min(hi - lo, L);
+        }
+        part[tid] = c;
+        __syncthreads();
+        imx_scan<IMX_PT>(part, tid);
+        if (b < B) out_ptr[b] = run + part[tid] - c;
+        run += part[IMX_PT - 1];
+        __syncthreads();
+    }
+    if (tid == 0) out_ptr[B] = run;
+}
+
+__device__ __forceinline__ unsigned int imx_key(unsigned int stream, unsigned int i, int shift) {
+    return gn_mix32(stream ^ (i * 0x85EBCA77u)) >> shift;
+}
+
+// both ice columns of one pulse: linear interpolation in fp64, one rounding per operation, NaN outside the table
+__device__ __forceinline__ void imx_ice(const double* tab, int T, float zf, float* sc, float* ab) {
+#pragma clang fp contract(off)
+    const double z = (double)zf;
+    const double* zt = tab;
+    if (!(z >= zt[0] && z <= zt[T - 1])) { *sc = *ab = __builtin_nanf(""); return; }
+    int l = 0, h = T - 1;                                   // zt[l] <= z, and z < zt[h] or h == T - 1
+    while (h - l > 1) {
+        const int mid = (l + h) >> 1;
+        if (zt[mid] <= z) l = mid; else h = mid;
+    }
+    const double dz = zt[l + 1] - zt[l], t = z - zt[l];
+    const double* ys = tab + T;
+    const double* ya = tab + 2 * T;
+    const double ss = (ys[l + 1] - ys[l]) / dz, sa = (ya[l + 1] - ya[l]) / dz;
+    const double ps = ss * t, pa = sa * t;
+    *sc = (float)(ps + ys[l]);
+    *ab = (float)(pa + ya[l]);
+}
+
+__global__ __launch_bounds__(PCT_NT) void imx_nodes_kernel(
+    const float* __restrict__ x, long long ldx, int F, const int* __restrict__ ptr, int N, int L, int hlc_col, int z_col,
+    const double* __restrict__ table, int T, unsigned int seed, const unsigned int* __restrict__ event_ids, int shift,
+    const int* __restrict__ out_ptr, float* __restrict__ out, long long ldo, int* ids)
+{
+    extern __shared__ __attribute__((aligned(16))) double imx_lds[];       // [3T table][256 ints][2 ints]
+    double* stab = imx_lds;
+    int* part = reinterpret_cast<int*>(imx_lds + 3 * T);
+    int* found = part + PCT_NT;
+    const int ev = (int)blockIdx.x, tid = (int)threadIdx.x;
+    const int hi = min(ptr[ev + 1], N), lo = min(max(ptr[ev], 0), hi);
+    const int n = hi - lo;
+    if (n <= 0) return;
+    const int ob = out_ptr[ev];
+    const int m = min(min(n, L), N - ob);                   // never more kept rows than pulses: nothing past row N - 1
+    for (int i = tid; i < 3 * T; i += PCT_NT) stab[i] = table[i];
+    if (n <= L) {
+        for (int r = tid; r < m; r += PCT_NT) ids[ob + r] = lo + r;
+    } else {
+        const unsigned int stream = gn_mix32(seed ^ ((event_ids ? event_ids[ev] : (unsigned int)ev) * 0x9E3779B1u));
+        unsigned int prefix = 0, mask = 0;
+        int r = L;                                          // the r-th smallest (from 1) among the keys that match prefix
+        for (int dshift = 24; dshift >= 0; dshift -= 8) {
+            part[tid] = 0;
+            __syncthreads();
+            for (int i = tid; i < n; i += PCT_NT) {
+                const unsigned int h = imx_key(stream, (unsigned int)i, shift);
+                if ((h & mask) == prefix) atomicAdd(&part[(h >> dshift) & 255u], 1);
+            }
+            __syncthreads();
+            const int mine = part[tid];
+            imx_scan<PCT_NT>(part, tid);
+            const int below = part[tid] - mine;
+            if (below < r && r <= part[tid]) { found[0] = tid; found[1] = below; }
+            __syncthreads();
+            prefix |= (unsigned int)found[0] << dshift;
+            mask |= 0xffu << dshift;
+            r -= found[1];
+            __syncthreads();
+        }
+        // prefix: the L-th smallest key; kept: every key below it and the r lowest-index pulses that have it
+        int lt_run = 0, eq_run = 0;
+        for (int base = 0; base < n; base += PCT_NT) {
+            const int i = base + tid;
+            int lt = 0, eq = 0;
+            if (i < n) {
+                const unsigned int h = imx_key(stream, (unsigned int)i, shift);
+                lt = h < prefix; eq = h == prefix;
+            }
+            const int mine = lt | (eq << 16);               // at most 256 of either in a chunk
+            part[tid] = mine;
+            __syncthreads();
+            imx_scan<PCT_NT>(part, tid);
+            const int before = part[tid] - mine;
+            const int lt_before = lt_run + (before & 0xffff), eq_before = eq_run + (before >> 16);
+            if (lt || (eq && eq_before < r)) {
+                const int pos = lt_before + min(eq_before, r);
+                if (pos < m) ids[ob + pos] = lo + i;
+            }
+            const int total = part[PCT_NT - 1];
+            lt_run += total & 0xffff; eq_run += total >> 16;
+            __syncthreads();
+        }
+    }
+    __syncthreads();                                        // the table and this event's ids
+    for (long long idx = tid; idx < (long long)m * F; idx += PCT_NT) {
+        const int r = (int)(idx / F), c = (int)(idx - (long long)r * F);
+        const int src = n <= L ? lo + r : ids[ob + r];
+        float v = x[(long long)src * ldx + c];
+        if (c == hlc_col) v = v == 0.0f ? 1.0f : 0.0f;
+        out[(long long)(ob + r) * ldo + c] = v;
+    }
+    if (z_col >= 0)
+        for (int r = tid; r < m; r += PCT_NT) {
+            const int src = n <= L ? lo + r : ids[ob + r];
+            float* o = out + (long long)(ob + r) * ldo + F;
+            imx_ice(stab, T, x[(long long)src * ldx + z_col], o, o + 1);
+        }
+}
+
+hipError_t launch_icemix_nodes(const float* x, long long ldx, int F, int N, const int* ptr, int B, int L, int hlc_col, int z_col,
+                               const double* table, int T, unsigned int seed, const unsigned int* event_ids, int key_bits,
+                               float* out, long long ldo, int* out_ptr, int* ids, hipStream_t st) {
+    if (B == 0) return hipSuccess;
+    if (N == 0) return hipMemsetAsync(out_ptr, 0, sizeof(int) * ((size_t)B + 1), st);
+    hipLaunchKernelGGL(imx_ptr_kernel, dim3(1), dim3(IMX_PT), 0, st, ptr, B, N, L, out_ptr);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const int Tl = z_col >= 0 ? T : 0;
+    const size_t lds = sizeof(double) * 3 * (size_t)Tl + sizeof(int) * (PCT_NT + 2);
+    hipLaunchKernelGGL(imx_nodes_kernel, dim3((unsigned)B), dim3(PCT_NT), lds, st, x, ldx, F, ptr, N, L, hlc_col, z_col, table,
+                       Tl, seed, event_ids, 32 - key_bits, out_ptr, out, ldo, ids);
     return hipGetLastError();
 }
 

@@ -1,8 +1,8 @@
 """Graph definitions: ``GraphDefinition`` / ``KNNGraph`` / ``KNNEdges`` / ``MinkowskiKNNEdges`` / ``RadialEdges`` /
-``NodesAsPulses`` / ``PercentileClusters`` / ``NodeAsDOMTimeSeries``.
+``NodesAsPulses`` / ``PercentileClusters`` / ``NodeAsDOMTimeSeries`` / ``IceMixNodes``.
 
 Host-side mirror of ``models/graphs/graph_definition.py:148-248``, ``graphs/graphs.py:13-58``,
-``graphs/edges/edges.py:47-117``, ``graphs/edges/minkowski.py:37-99`` and ``graphs/nodes/nodes.py:22-306``.
+``graphs/edges/edges.py:47-117``, ``graphs/edges/minkowski.py:37-99`` and ``graphs/nodes/nodes.py:22-453``.
 
 Difference by design: the reference builds k-NN edges on the CPU, one event
 at a time, inside DataLoader workers.  Here a CPU ``Data`` leaves ``edge_index`` unset and the
@@ -12,6 +12,8 @@ There is no CPU k-NN in this package.
 """
 from __future__ import annotations
 
+import os
+import warnings
 from typing import Any, Callable, Dict, List, Optional, Tuple, Union
 
 import numpy as np
@@ -264,6 +266,210 @@ class NodeAsDOMTimeSeries(NodeDefinition):
     def _construct_nodes(self, x: torch.Tensor) -> Data:
         ptr = torch.tensor([0, int(x.shape[0])], dtype=torch.int32, device=x.device)
         return Data(x=self.series_batch(x, ptr)[0])
+
+_M32 = np.uint64(0xFFFFFFFF)
+
+
+def _mix32(v: np.ndarray) -> np.ndarray:
+    """``gn_mix32`` of ``graphnet_amd/csrc/common.hpp`` on uint32 values held in uint64 arrays."""
+    v = v ^ (v >> np.uint64(16))
+    v = (v * np.uint64(0x21F0AAAD)) & _M32
+    v = v ^ (v >> np.uint64(15))
+    v = (v * np.uint64(0x735A2D97)) & _M32
+    return v ^ (v >> np.uint64(15))
+
+
+def icemix_keys(seed: int, event_id: int, n: int, key_bits: int = 32) -> np.ndarray:
+    """The sampling key of every pulse of one event (``gn_icemix_nodes``): uint64 ``[n]`` holding uint32 values."""
+    stream = _mix32(np.uint64(seed & 0xFFFFFFFF) ^ ((np.uint64(event_id & 0xFFFFFFFF) * np.uint64(0x9E3779B1)) & _M32))
+    i = np.arange(n, dtype=np.uint64)
+    return _mix32(stream ^ ((i * np.uint64(0x85EBCA77)) & _M32)) >> np.uint64(32 - key_bits)
+
+
+def ice_table_host(depth: np.ndarray, scattering_len: np.ndarray, absorption_len: np.ndarray,
+                   z_offset: Optional[float] = None, z_scaling: Optional[float] = None) -> np.ndarray:
+    """What the reference's ``ice_transparency`` (``models/graphs/utils.py:175-209``) builds its two ``interp1d``
+    functions from, as fp64 ``[3, T]``: the knots ``(depth + (z_offset or -1950)) / (z_scaling or 500)`` ascending, then both
+    lengths through sklearn's ``RobustScaler`` - ``(v - median) / (q75 - q25)``, which is all that scaler does to one
+    column, in numpy alone."""
+    z = (np.asarray(depth, dtype=np.float64) + (z_offset or -1950.0)) / (z_scaling or 500.0)
+    cols = [z]
+    for v in (scattering_len, absorption_len):
+        v = np.asarray(v, dtype=np.float64)
+        cols.append((v - np.median(v)) / (np.percentile(v, 75) - np.percentile(v, 25)))
+    table = np.stack(cols)[:, np.argsort(z, kind="stable")]           # interp1d sorts its knots
+    if table.shape[1] < 2 or not (np.diff(table[0]) > 0).all():
+        raise ValueError("ice table: need at least two rows and distinct depths")
+    return np.ascontiguousarray(table)
+
+
+def ice_interp_host(table: np.ndarray, z: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """Both ice functions at the fp32 depths ``z``, in fp64 (the contract of ``gn_icemix_nodes``: interval ``j`` = the largest
+    index with ``zt[j] <= z``, at most ``T - 2``; ``slope = (y[j+1] - y[j]) / (zt[j+1] - zt[j])``; ``slope * (z - zt[j]) + y[j]``).
+    A depth outside the table, or NaN, raises ``ValueError`` as the reference's ``interp1d`` does."""
+    zt = table[0]
+    z = np.asarray(z, dtype=np.float32).astype(np.float64)
+    if not ((z >= zt[0]) & (z <= zt[-1])).all():
+        raise ValueError(f"A value in the z column is outside the interpolation range [{zt[0]}, {zt[-1]}] of the ice table")
+    j = np.clip(np.searchsorted(zt, z, side="right") - 1, 0, len(zt) - 2)
+    dz, t = zt[j + 1] - zt[j], z - zt[j]
+    return tuple(((y[j + 1] - y[j]) / dz) * t + y[j] for y in (table[1], table[2]))
+
+
+def icemix_nodes_host(x: np.ndarray, ptr: np.ndarray, max_pulses: int, hlc_col: int = -1, z_col: int = -1,
+                      table: Optional[np.ndarray] = None, seed: int = 0, event_ids: Optional[np.ndarray] = None,
+                      key_bits: int = 32) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """The contract of ``gn_icemix_nodes`` (``include/graphnet_amd.h``) for a whole batch in vectorised numpy: fp32
+    ``[N, F]`` -> ``(nodes fp32 [M, F + 2*(z_col >= 0)], node_ptr int32 [B + 1], ids int32 [M])``.  Bit for bit what the
+    kernel writes, but that a depth outside the ice table raises ``ValueError`` here and is NaN there."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    bounds = np.asarray(ptr, dtype=np.int64)
+    L, B, F = int(max_pulses), len(bounds) - 1, x.shape[1]
+    kept = []
+    for b in range(B):
+        lo, n = int(bounds[b]), int(bounds[b + 1] - bounds[b])
+        if n <= L:
+            kept.append(lo + np.arange(n, dtype=np.int64))
+        else:       # the L smallest in the total order (key, index), then back in pulse order
+            h = icemix_keys(seed, b if event_ids is None else int(event_ids[b]), n, key_bits)
+            kept.append(lo + np.sort(np.argsort(h, kind="stable")[:L]))
+    node_ptr = np.zeros(B + 1, dtype=np.int32)
+    node_ptr[1:] = np.cumsum([len(k) for k in kept])
+    ids = np.concatenate(kept).astype(np.int32) if kept else np.zeros(0, dtype=np.int32)
+    out = np.zeros((len(ids), F + (2 if z_col >= 0 else 0)), dtype=np.float32)
+    out[:, :F] = x[ids]
+    if hlc_col >= 0:
+        out[:, hlc_col] = x[ids, hlc_col] == 0
+    if z_col >= 0:
+        out[:, F], out[:, F + 1] = ice_interp_host(table, x[ids, z_col])
+    return out, node_ptr, ids
+
+
+def _read_ice_table(path: str) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    names = ("depth", "scattering_len", "absorption_len")
+    if path.endswith(".npz"):
+        d = np.load(path)
+        return tuple(np.asarray(d[k], dtype=np.float64) for k in names)
+    import pandas as pd
+    df = pd.read_parquet(path)
+    return tuple(np.asarray(df[k], dtype=np.float64) for k in names)
+
+
+def _find_ice_table() -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    path = os.environ.get("GRAPHNET_AMD_ICE_TABLE")
+    if path:
+        return _read_ice_table(path)
+    try:
+        from graphnet.constants import DATA_DIR
+    except Exception:
+        DATA_DIR = None
+    if DATA_DIR is not None:
+        return _read_ice_table(os.path.join(DATA_DIR, "ice_properties", "ice_transparency.parquet"))
+    raise RuntimeError(
+        "IceMixNodes(add_ice_properties=True) needs the ice transparency table, which this package does not ship: set "
+        "$GRAPHNET_AMD_ICE_TABLE to the reference's data/ice_properties/ice_transparency.parquet (or an .npz with the "
+        "columns depth, scattering_len, absorption_len), assign IceMixNodes.ice_table = (depth, scattering_len, "
+        "absorption_len) before constructing (or on an instance, to replace its table), or install graphnet, whose "
+        "DATA_DIR is then used")
+
+
+class IceMixNodes(NodeDefinition):
+    """Ice properties and random pulse sampling (``nodes/nodes.py:309-453``; argument names, order and defaults are the
+    reference's, ``scatt_lenght`` / ``abs_lenght`` are its spelling).  Per event: the ``hlc_name`` column becomes its
+    logical not, an event of more than ``max_pulses`` pulses keeps ``max_pulses`` of them, and with
+    ``add_ice_properties`` two columns are appended: the scattering and absorption length of the ice at the pulse's
+    ``z_name``, linear interpolation in fp64 of the reference's table after ``RobustScaler``.  The arithmetic is defined
+    operation by operation in ``include/graphnet_amd.h`` (``gn_icemix_nodes``).  A device tensor takes one
+    ``gn_icemix_nodes`` call; a CPU tensor takes :func:`icemix_nodes_host`, the same contract in numpy, ids and rows bit
+    for bit.  On the device a whole batch is sampled by one call: ``GraphDefinition.batch_from_raw``, whose batch also
+    carries ``pulse_ids``.
+
+    **Which pulses are kept.**  A uniformly random ``max_pulses``-subset of the event, in pulse order, whatever the hlc
+    column holds.  That is the reference's distribution: it draws ``ids = randperm(n)`` and takes ``ids[auxiliary_n]`` and
+    ``ids[auxiliary_p]`` - the PERMUTATION at the positions of the flagged pulses, not the flagged pulses - so the two
+    parts are disjoint random ids unrelated to hlc, and their sorted union is a uniform subset.  There is no hlc-priority
+    option here either.  The subset is a function of ``(seed, event id, pulse index)`` through the library's counter
+    hash, not torch's generator stream.  One definition where the reference differs: with ``hlc_name=None`` it keeps
+    the subset in random order; here the rows are always in pulse order.
+
+    **The ice table** is data of the reference and is not shipped: it is read from ``$GRAPHNET_AMD_ICE_TABLE`` (the
+    reference's parquet, or an ``.npz`` with the columns ``depth``, ``scattering_len``, ``absorption_len``), taken from
+    ``ice_table`` when that was assigned (on the class before construction, or on an instance to replace its table), or
+    read from the reference's ``DATA_DIR`` when ``graphnet`` is importable; otherwise construction with
+    ``add_ice_properties=True`` raises.  A z outside the table raises ``ValueError`` on the host, as in the reference; the
+    kernel cannot raise and writes NaN into both ice columns."""
+
+    ice_table: Optional[Tuple[np.ndarray, np.ndarray, np.ndarray]] = None
+
+    def __init__(self, input_feature_names: Optional[List[str]] = None, max_pulses: int = 768, z_name: str = "dom_z",
+                 hlc_name: Optional[str] = "hlc", add_ice_properties: bool = True,
+                 ice_args: Dict[str, Optional[float]] = {"z_offset": None, "z_scaling": None}) -> None:
+        if input_feature_names is None:
+            input_feature_names = ["dom_x", "dom_y", "dom_z", "dom_time", "charge", "hlc", "rde"]
+        input_feature_names = list(input_feature_names)
+        if add_ice_properties:
+            if z_name not in input_feature_names:
+                raise ValueError(f"z name '{z_name}' not found in input_feature_names {input_feature_names}")
+            self.all_features = input_feature_names + ["scatt_lenght", "abs_lenght"]
+            if self.ice_table is None:
+                self.ice_table = _find_ice_table()
+        else:
+            self.all_features = input_feature_names
+        self._ice_args = dict(ice_args)
+        self._table_cache: Dict[Any, Any] = {}
+        super().__init__(input_feature_names=input_feature_names)
+        if hlc_name not in input_feature_names:
+            warnings.warn(f"hlc name '{hlc_name}' not found in input_feature_names '{input_feature_names}', "
+                          "subsampling will be random.")
+            hlc_name = None
+        self.feature_indexes = {feat: self.all_features.index(feat) for feat in input_feature_names}
+        self.input_feature_names = input_feature_names
+        self.n_features = len(self.all_features)
+        self.max_length = max_pulses
+        self.z_name = z_name
+        self.hlc_name = hlc_name
+        self.add_ice_properties = add_ice_properties
+
+    def _define_output_feature_names(self, input_feature_names: List[str]) -> List[str]:
+        return self.all_features
+
+    def _table(self, device: Any = None) -> Any:
+        """fp64 ``[3, T]`` of :func:`ice_table_host` for the present ``ice_table`` (numpy, or a tensor on ``device``)."""
+        if self._table_cache.get("source") is not self.ice_table:
+            self._table_cache = {"source": self.ice_table, None: ice_table_host(*self.ice_table, **self._ice_args)}
+        if device not in self._table_cache:
+            self._table_cache[device] = torch.from_numpy(self._table_cache[None]).to(device)
+        return self._table_cache[device]
+
+    def f_scattering(self, z: Any) -> np.ndarray:
+        return ice_interp_host(self._table(), np.asarray(z))[0]
+
+    def f_absoprtion(self, z: Any) -> np.ndarray:
+        return ice_interp_host(self._table(), np.asarray(z))[1]
+
+    def sample_batch(self, x: torch.Tensor, ptr: torch.Tensor, seed: Optional[int] = None,
+                     event_ids: Optional[Any] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """``(nodes fp32 [M, n_features], node_ptr int32 [B + 1], ids int32 [M])`` of the events ``ptr`` marks in ``x``;
+        ``ids`` is the row of ``x`` behind every node.  One device call, or the host path for a CPU tensor.  ``seed=None``
+        draws one uint32 from torch's global CPU generator, so ``torch.manual_seed`` reproduces a run and successive calls
+        differ; ``event_ids`` (``[B]`` integers, by default the ordinals) name the stream of each event."""
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 32, (1,), dtype=torch.int64).item())
+        hlc = -1 if self.hlc_name is None else self.feature_indexes[self.hlc_name]
+        z = self.feature_indexes[self.z_name] if self.add_ice_properties else -1
+        if x.is_cuda:
+            from . import ops
+            ev = None if event_ids is None else torch.as_tensor(event_ids)
+            return ops.icemix_nodes(x.to(torch.float32), ptr.to(torch.int32), self.max_length, hlc, z,
+                                    self._table(x.device) if z >= 0 else None, seed, ev)
+        ev = None if event_ids is None else np.asarray(torch.as_tensor(event_ids).cpu().numpy(), dtype=np.int64)
+        nodes, node_ptr, ids = icemix_nodes_host(x.detach().to(torch.float32).numpy(), ptr.cpu().numpy(), self.max_length, hlc,
+                                                 z, self._table() if z >= 0 else None, seed, ev)
+        return torch.from_numpy(nodes), torch.from_numpy(node_ptr), torch.from_numpy(ids)
+
+    def _construct_nodes(self, x: torch.Tensor) -> Data:
+        ptr = torch.tensor([0, int(x.shape[0])], dtype=torch.int32, device=x.device)
+        return Data(x=self.sample_batch(x, ptr)[0])
 
 
 class EdgeDefinition(Model):
@@ -645,6 +851,9 @@ def _batch_from_raw(self: "GraphDefinition", events: "List[np.ndarray]", input_f
     ``gn_percentile_clusters`` call: ``x`` / ``ptr`` / ``batch`` describe the clusters, ``n_pulses`` the raw pulses.
     With a :class:`NodeAsDOMTimeSeries` node definition it goes through one ``gn_dom_time_series`` call: the rows stay
     pulses (``x`` / ``ptr`` / ``batch`` / ``n_pulses``), and the batch also carries ``series_ptr`` / ``dom_ptr``.
+    With an :class:`IceMixNodes` node definition it goes through one ``gn_icemix_nodes`` call: ``x`` / ``ptr`` / ``batch``
+    describe the kept pulses, ``n_pulses`` the raw pulses, and ``pulse_ids`` names the row of the standardised batch behind
+    every kept pulse (for truth per pulse).
     ``truth``: name -> per-event sequence (filtered alongside)."""
     from .data import Batch
     keep = [i for i, e in enumerate(events) if len(e) > 1]
@@ -687,9 +896,19 @@ def _batch_from_raw(self: "GraphDefinition", events: "List[np.ndarray]", input_f
         b.batch = torch.repeat_interleave(torch.arange(len(keep), dtype=torch.int64), torch.from_numpy(sizes)).to(device)
         b.series_ptr = series_ptr
         b.dom_ptr = dom_ptr
+    elif isinstance(nd, IceMixNodes):
+        # one sampling call over the whole batch: ptr / batch describe the kept rows, n_pulses stays the raw pulses
+        nodes, node_ptr, ids = nd.sample_batch(x, torch.from_numpy(ptr).to(torch.int32).to(x.device))
+        b = Batch(x=nodes.type(self.dtype))
+        b.ptr = node_ptr.to(torch.int64)
+        b.n_pulses = n_pulses.to(device)
+        b.batch = torch.repeat_interleave(torch.arange(len(keep), dtype=torch.int64, device=b.ptr.device),
+                                          b.ptr[1:] - b.ptr[:-1], output_size=int(nodes.shape[0]))
+        b.pulse_ids = ids
     else:
-        raise NotImplementedError(f"graphnet_amd: batch_from_raw builds NodesAsPulses, PercentileClusters and "
-                                  f"NodeAsDOMTimeSeries nodes, not {nd.__class__.__name__}; use the per-event path")
+        raise NotImplementedError(f"graphnet_amd: batch_from_raw builds NodesAsPulses, PercentileClusters, "
+                                  f"NodeAsDOMTimeSeries and IceMixNodes nodes, not {nd.__class__.__name__}; use the "
+                                  "per-event path")
     ed = self._edge_definition
     if ed is not None and hasattr(ed, "_nb_nearest_neighbours"):
         b.knn_k = int(ed._nb_nearest_neighbours)

@@ -377,6 +377,51 @@ def dom_time_series(x: Tensor, ptr: Tensor, id_cols: Sequence[int], time_col: in
     return out[:, :W], series_ptr[:M + 1], dom_ptr
 
 
+def icemix_nodes(x: Tensor, ptr: Tensor, max_pulses: int, hlc_col: int = -1, z_col: int = -1,
+                 table: Optional[Tensor] = None, seed: int = 0, event_ids: Optional[Tensor] = None, key_bits: int = 32,
+                 out_pitch: Optional[int] = None) -> Tuple[Tensor, Tensor, Tensor]:
+    """Batched pulse sampling with ice properties (``gn_icemix_nodes``; the reference's ``IceMixNodes``,
+    ``graphs/nodes/nodes.py:309-453``): every event of ``ptr`` (int32 ``[B + 1]``) keeps a uniformly random ``max_pulses``
+    of its rows of ``x`` (fp32) in their order, column ``hlc_col`` becomes its logical not and, with ``z_col >= 0``, two
+    columns interpolated from ``table`` (fp64 ``[3, T]`` on the device: knots, scattering, absorption) are appended.
+    Returns ``(nodes[M, W], node_ptr int32 [B + 1], ids int32 [M])``, ``ids`` the row of ``x`` behind every node: one call,
+    one read-back (``M``).  ``event_ids`` (``[B]`` integers, by default the event ordinals) name the random stream of each
+    event; ``key_bits`` below 32 only serves tests.  The contract is spelled out in ``include/graphnet_amd.h``."""
+    _need(x, torch.float32, "x"); _need(ptr, torch.int32, "ptr")
+    N, F, B = int(x.shape[0]), int(x.shape[1]), int(ptr.shape[0]) - 1
+    W = F + (2 if z_col >= 0 else 0)
+    ldo = W if out_pitch is None else int(out_pitch)
+    if ldo < W:
+        raise ValueError(f"icemix_nodes: out_pitch {ldo} < {W} columns")
+    T = 0
+    if z_col >= 0:
+        if table is None:
+            raise ValueError("icemix_nodes: the ice columns need table[3, T]")
+        _need(table, torch.float64, "table")
+        T = int(table.shape[1]) if table.dim() == 2 and table.shape[0] == 3 and table.is_contiguous() else -1
+        if not 2 <= T <= 1024:
+            raise ValueError(f"icemix_nodes: table must be a contiguous fp64 [3, T] with 2 <= T <= 1024, got {tuple(table.shape)}")
+    if event_ids is not None:
+        if int(event_ids.numel()) != max(B, 0):
+            raise ValueError(f"icemix_nodes: event_ids has {int(event_ids.numel())} entries for {B} events")
+        # uint32 values in an int32 tensor (two's complement): torch has no arithmetic on uint32
+        event_ids = (event_ids.to(device=x.device, dtype=torch.int64) & 0xFFFFFFFF).to(torch.int32).contiguous()
+    if N == 0 or B <= 0:
+        return (torch.empty((0, ldo), dtype=torch.float32, device=x.device)[:, :W],
+                torch.zeros(max(B, 0) + 1, dtype=torch.int32, device=x.device),
+                torch.empty(0, dtype=torch.int32, device=x.device))
+    ld = _rows(x, "x")
+    out = torch.empty((N, ldo), dtype=torch.float32, device=x.device)
+    node_ptr = torch.empty(B + 1, dtype=torch.int32, device=x.device)
+    ids = torch.empty(N, dtype=torch.int32, device=x.device)
+    with _timed("icemix_nodes"):
+        _lib.check(_lib.lib().gn_icemix_nodes(_p(x), ld, F, N, _p(ptr), B, int(max_pulses), int(hlc_col), int(z_col),
+                                              _p(table) if z_col >= 0 else None, T, int(seed) & 0xFFFFFFFF, _p(event_ids),
+                                              int(key_bits), _p(out), ldo, _p(node_ptr), _p(ids), _st()))
+    M = int(node_ptr[B].item())
+    return out[:M, :W], node_ptr, ids[:M]
+
+
 def gru_supported(input_size: int, hidden_size: int) -> bool:
     return bool(_lib.lib().gn_gru_supported(int(input_size), int(hidden_size)))
 

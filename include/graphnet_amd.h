@@ -131,7 +131,35 @@ int gn_dom_time_series(const float* x, int64_t ldx, int32_t F, int32_t N, const 
                        const int32_t* id_cols_host, int32_t C, int32_t time_col, int32_t charge_col,
                        float* out, int64_t ldo, int32_t* series_ptr, int32_t* dom_ptr, int32_t* work, void* stream);
 
-/* Ragged GRU recurrence over series (models/rnn/node_rnn.py:105-111; layer 0 of torch.nn.GRU).  Series s owns rows
+/* IceMixNodes (models/graphs/nodes/nodes.py:309-453): every event cut to at most L = max_pulses of its pulses, the hlc column
+ * flipped, two ice columns interpolated from a table.  x[N, ldx] with F feature columns, fp32 in and out, out must not overlap
+ * x; ptr[B+1] ascending with ptr[0] = 0 and ptr[B] = N; empty events are legal.  Per event b with n pulses:
+ *   key of pulse i (its index INSIDE the event): stream e = event_ids ? event_ids[b] : b (uint32), and
+ *     h = gn_mix32(gn_mix32(seed ^ e*0x9E3779B1) ^ i*0x85EBCA77) >> (32 - key_bits)         all in uint32 arithmetic;
+ *     gn_mix32(v): v ^= v >> 16; v *= 0x21F0AAAD; v ^= v >> 15; v *= 0x735A2D97; v ^= v >> 15   (the dropout hash, (a, b) = (e, i)).
+ *   selection: n <= L keeps every pulse; otherwise pulse i is kept iff fewer than L pulses of the event precede it in the
+ *     total order (h, i).  Rows are written in ascending i in both cases.  (The reference draws randperm(n) and indexes it at
+ *     the flagged positions, which is a uniformly random L-subset whatever the hlc column holds, sorted when there is an hlc
+ *     column and in random order when there is none; the contract here is that distribution, always ascending, and not
+ *     torch's generator stream.)  key_bits is 32 in production; fewer bits force equal keys, for tests of the tie rule.
+ *   row of kept pulse id (a row of x): out[., c] = x[id, c] bit for bit for c < F, but
+ *     c == hlc_col: x[id, c] == 0 ? 1.0f : 0.0f     (logical_not; a NaN gives 0);
+ *     z_col >= 0: two more columns, F (scattering) and F + 1 (absorption), from table = zt[T] | ys[T] | ya[T] (doubles, zt
+ *       strictly ascending, ys / ya already scaled).  z = (double) x[id, z_col]; j = the largest index with zt[j] <= z, at
+ *       most T - 2 (so z == zt[T-1] lies in the last interval); fp64, one rounding per operation, no FMA contraction:
+ *         slope = (y[j+1] - y[j]) / (zt[j+1] - zt[j]);  v = slope * (z - zt[j]) + y[j];  out = (float) v
+ *       z < zt[0], z > zt[T-1] or NaN: NaN in both columns (a kernel cannot raise; the host path of the package does).
+ *   W = F + 2*(z_col >= 0) columns.
+ * out[M, ldo] and ids[M], M = sum_b min(n_b, L) <= N (room for N rows always suffices; nothing is written past row N - 1);
+ * out_ptr[B+1]: row offsets per event, out_ptr[B] = M; ids[r]: the row of x that output row r came from.
+ * table: DEVICE pointer (unused with z_col = -1), 2 <= T <= 1024; event_ids: DEVICE uint32[B] or NULL; hlc_col / z_col < F
+ * (-1: none); max_pulses >= 1; 1 <= key_bits <= 32; ldo >= W; N <= 2^28.  No work buffer and no limit on the size of an
+ * event; integer LDS atomics only: two runs agree bit for bit. */
+int gn_icemix_nodes(const float* x, int64_t ldx, int32_t F, int32_t N, const int32_t* ptr, int32_t B, int32_t max_pulses,
+                    int32_t hlc_col, int32_t z_col, const double* table, int32_t T, uint32_t seed, const uint32_t* event_ids,
+                    int32_t key_bits, float* out, int64_t ldo, int32_t* out_ptr, int32_t* ids, void* stream);
+
+/* Ragged GRU recurrence over series(models/rnn/node_rnn.py:105-111; layer 0 of torch.nn.GRU).  Series s owns rows
  * series_ptr[s] .. series_ptr[s+1] of xs[T, ldx] (I columns); series_ptr[0] = 0, series_ptr[M] = T, no empty series.  Gate
  * order and tensors are torch.nn.GRU's: r, z, n; weight_ih[3H, I], weight_hh[3H, H], bias_ih[3H], bias_hh[3H], contiguous.
  * h = 0, then for every row t of the series

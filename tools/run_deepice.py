@@ -5,7 +5,11 @@ IceCubeKaggle standardisation): fwd + bwd + AdamW per step of the backbone alone
 n_rel = 1 (the shipped value) and n_rel = 4.  The biased attention (gn_rel_attention_fwd / _bwd) is also timed on its own with
 device events, beside the plain ragged attention (fp32 and bf16 kernels) on the same batch and the same qkv.
 
-usage: run_deepice.py [B] [fp32|bf16] [steps]"""
+--icemix builds the batch as a user of the reference does, through IceMixNodes(max_pulses=192) on the device (one
+gn_icemix_nodes call: a random 192 of each longer event, the auxiliary flag flipped) in place of the host loop that keeps the
+first 192; the default workload is the host loop, so that its numbers stay comparable with earlier ones.
+
+usage: run_deepice.py [B] [fp32|bf16] [steps] [--icemix]"""
 import json
 import os
 import sys
@@ -19,23 +23,37 @@ import graphnet_amd as g                                              # noqa: E4
 from graphnet_amd import ops                                          # noqa: E402
 from graphnet_amd.synthetic import synthetic_icecube86_raw            # noqa: E402
 
-B = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
-dtype = sys.argv[2] if len(sys.argv) > 2 else "bf16"
-steps = int(sys.argv[3]) if len(sys.argv) > 3 else 10
+ICEMIX = "--icemix" in sys.argv
+argv = [a for a in sys.argv if a != "--icemix"]
+B = int(argv[1]) if len(argv) > 1 else 1024
+dtype = argv[2] if len(argv) > 2 else "bf16"
+steps = int(argv[3]) if len(argv) > 3 else 10
 MAX_PULSES, HIDDEN, HEAD = 192, 768, 32
 torch.manual_seed(0)
 
+NAMES = ["x", "y", "z", "time", "charge", "auxiliary"]
 raw, ptr, _ = synthetic_icecube86_raw(B, seed=5)
-keep = np.concatenate([np.arange(ptr[i], min(ptr[i + 1], ptr[i] + MAX_PULSES)) for i in range(B)])      # the first 192 pulses
-n = np.minimum(ptr[1:] - ptr[:-1], MAX_PULSES)
-x = torch.from_numpy(raw[keep][:, :6].copy())
-x[:, 5] = (torch.rand(x.shape[0]) < 0.3).float()                      # auxiliary flag
-x = g.IceCubeKaggle()(x, ["x", "y", "z", "time", "charge", "auxiliary"])
-ptr_t = torch.from_numpy(np.concatenate([[0], np.cumsum(n)])).to(torch.int64)
-batch = g.Batch(x=x.to("cuda"))
-batch.ptr = ptr_t.to("cuda")
-batch.batch = torch.repeat_interleave(torch.arange(B), torch.from_numpy(n)).to("cuda")
-batch.n_pulses = torch.from_numpy(n).to(torch.int32).to("cuda")
+if ICEMIX:
+    raw = raw[:, :6].copy()
+    raw[:, 5] = (torch.rand(raw.shape[0]) < 0.3).float().numpy()     # auxiliary flag
+    nodes = g.IceMixNodes(input_feature_names=NAMES, max_pulses=MAX_PULSES, z_name="z", hlc_name="auxiliary",
+                          add_ice_properties=False)                  # DeepIce reads the first six columns
+    batch = g.KNNGraph(g.IceCubeKaggle(), node_definition=nodes, input_feature_names=NAMES).batch_from_raw(
+        [raw[ptr[i]:ptr[i + 1]] for i in range(B)], NAMES, device="cuda")
+    n = (batch.ptr[1:] - batch.ptr[:-1]).cpu().numpy()
+    B = len(n)                                                        # events of one pulse are dropped
+    x = batch.x
+else:
+    keep = np.concatenate([np.arange(ptr[i], min(ptr[i + 1], ptr[i] + MAX_PULSES)) for i in range(B)])      # the first 192 pulses
+    n = np.minimum(ptr[1:] - ptr[:-1], MAX_PULSES)
+    x = torch.from_numpy(raw[keep][:, :6].copy())
+    x[:, 5] = (torch.rand(x.shape[0]) < 0.3).float()                      # auxiliary flag
+    x = g.IceCubeKaggle()(x, NAMES)
+    ptr_t = torch.from_numpy(np.concatenate([[0], np.cumsum(n)])).to(torch.int64)
+    batch = g.Batch(x=x.to("cuda"))
+    batch.ptr = ptr_t.to("cuda")
+    batch.batch = torch.repeat_interleave(torch.arange(B), torch.from_numpy(n)).to("cuda")
+    batch.n_pulses = torch.from_numpy(n).to(torch.int32).to("cuda")
 N = int(x.shape[0])
 pairs = int((n.astype(np.int64) ** 2).sum())
 
