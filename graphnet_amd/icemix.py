@@ -5,8 +5,8 @@ constructor signatures, defaults and sub-module names, hence the same state-dict
 ``[B, L, d]``, materialises the spacetime bias as ``[B, L, L, head_size]`` fp32 and contracts it twice per layer.  Here the
 batch stays ragged (``x``, ``ptr``) and neither tensor exists:
 
-* blocks with the spacetime bias run on ``csrc/attn_rel.hip``.  With ``s_ij`` the sinusoidal embedding of the clipped
-  4-distance and ``R_ij = W s_ij + b`` (``rel_pos.projection``), ``q~ . k + q~ . R_ij = q~ . k + (W^T q~) . s_ij + const`` and
+* blocks with the spacetime bias run on ``csrc/attn_rel.hip`` (head width 32) or ``csrc/attn_rel_wide.hip`` (64).
+  With ``s_ij`` the sinusoidal embedding of the clipped 4-distance and ``R_ij = W s_ij + b`` (``rel_pos.projection``), ``q~ . k + q~ . R_ij = q~ . k + (W^T q~) . s_ij + const`` and
   ``sum_j a_ij (v_j + R_ij) = O_i + W U_i + b`` with ``U_i = sum_j a_ij s_ij``: the kernel takes ``q, k, v`` and ``q' = W^T q~``,
   recomputes ``s_ij`` per pair and returns ``O`` and ``U``; ``W`` and ``b`` stay in two small GEMMs with plain autograd;
 * blocks without it (the rest of ``sandwich``, and ``blocks`` with the cls row of every event) run on ``csrc/attn.hip``;
@@ -49,23 +49,31 @@ class _RaggedAttentionFunction(torch.autograd.Function):
 
 
 class _RelAttentionFunction(torch.autograd.Function):
-    """Ragged attention with the spacetime bias recomputed per pair (``ops.rel_attention_fwd`` / ``rel_attention_bwd``):
-    (qkv ``[N, 3 d]``, qp ``[N, d]``) -> (out, u), both ``[N, d]``; ``xt`` and ``freq`` are data."""
+    """Ragged attention with the spacetime bias recomputed per pair (``ops.rel_attention_fwd`` / ``rel_attention_bwd``, at
+    head width 64 ``ops.rel_attention_wide_fwd`` / ``rel_attention_wide_bwd``): (qkv ``[N, 3 d]``, qp ``[N, d]``) -> (out, u),
+    both ``[N, d]``; ``xt`` and ``freq`` are data."""
 
     @staticmethod
     def forward(ctx, qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, ptr: Tensor, plan: Tensor):  # type: ignore[override]
         qkv, qp = qkv.contiguous(), qp.contiguous()
-        out, u, lse2 = ops.rel_attention_fwd(qkv, qp, xt, freq, n_head, ptr, plan)
+        wide = ops.rel_attention_wide_supported(int(qp.shape[1]) // n_head)
+        out, u, lse2 = (ops.rel_attention_wide_fwd if wide else ops.rel_attention_fwd)(qkv, qp, xt, freq, n_head, ptr, plan)
         ctx.save_for_backward(qkv, qp, xt, freq, ptr, plan, out, u, lse2)
-        ctx.n_head = n_head
+        ctx.n_head, ctx.wide = n_head, wide
         return out, u
 
     @staticmethod
     def backward(ctx, dout: Tensor, du: Tensor):  # type: ignore[override]
         qkv, qp, xt, freq, ptr, plan, out, u, lse2 = ctx.saved_tensors
-        dqkv, dqp = ops.rel_attention_bwd(qkv, qp, xt, freq, ctx.n_head, ptr, plan, out, u, lse2,
-                                          dout.contiguous().to(torch.float32), du.contiguous().to(torch.float32))
+        bwd = ops.rel_attention_wide_bwd if ctx.wide else ops.rel_attention_bwd
+        dqkv, dqp = bwd(qkv, qp, xt, freq, ctx.n_head, ptr, plan, out, u, lse2, dout.contiguous().to(torch.float32),
+                        du.contiguous().to(torch.float32))
         return dqkv, dqp, None, None, None, None, None
+
+
+def _rel_width_built(dh: int) -> bool:
+    """Head widths of the biased attention: 32 (one lane per query) and 64 (two lanes per query)."""
+    return ops.rel_attention_supported(dh) or ops.rel_attention_wide_supported(dh)
 
 
 def _linear(x: Tensor, weight: Tensor, bias: Optional[Tensor], mode: int) -> Tensor:
@@ -249,9 +257,9 @@ class Attention_rel(Model):
         else:
             if int(rel.projection.weight.shape[0]) != dh:
                 raise ValueError(f"Attention_rel: the spacetime encoder is {rel.projection.weight.shape[0]} wide, the heads {dh}")
-            if not ops.rel_attention_supported(dh):
-                raise NotImplementedError(f"graphnet_amd.Attention_rel: the biased attention kernels are built for head width "
-                                          f"32, not {dh}; there is no fallback")
+            if not _rel_width_built(dh):
+                raise NotImplementedError(f"graphnet_amd.Attention_rel: the biased attention kernels are built for head widths "
+                                          f"32 and 64, not {dh}; there is no fallback")
             qkv = qkv.to(torch.float32)
             Wr, br = rel.projection.weight, rel.projection.bias                  # R_ij = Wr s_ij + br
             qp = torch.matmul(qkv[:, :d].reshape(N, H, dh) * self.scale, Wr).reshape(N, d)      # W^T q~ per head
@@ -374,9 +382,9 @@ class DeepIce(GNN):
         N, dev, mode = int(x.shape[0]), x.device, self._compute_mode
         if int(x.shape[1]) < self.fourier_ext.n_features:
             raise ValueError(f"DeepIce(n_features={self.fourier_ext.n_features}): the batch has {int(x.shape[1])} columns")
-        if not ops.rel_attention_supported(self._head_size):
+        if not _rel_width_built(self._head_size):
             raise NotImplementedError(f"graphnet_amd.DeepIce: head_size {self._head_size} is outside the biased attention "
-                                      "kernels' envelope (32); there is no fallback")
+                                      "kernels' envelope (32 and 64); there is no fallback")
         ptr = _maybe(data, "ptr")
         batch = _maybe(data, "batch")
         if ptr is None:

@@ -534,6 +534,26 @@ int gn_rel_attention_bwd(const float* qkv, int64_t ld, const float* qp, int64_t 
                          int64_t lddo, const float* du, int64_t lddu, const float* lse2, float* delta, float* dqkv,
                          int64_t lddq, float* dqp, int64_t lddqp, void* stream);
 
+/* The same for DH = 64 (gn_rel_attention_wide_supported; the IceMix d64 shapes), a kernel family of its own: arguments,
+ * validation, pair-argument contract and results as above, gn_rel_attention_supported(64) stays 0.
+ * Ownership: one workgroup of 128 threads per (64-row tile of the plan, head); wave w holds rows 32 w .. 32 w + 31 of the
+ * tile, lanes l and l ^ 32 of a wave are the halves h = l / 32 of one row (a query in the forward and the dQ pass, a key in
+ * the dK / dV pass).  Half h holds columns [32 h, 32 h + 32) of q, k, v, out, dout and their gradients, and frequencies
+ * [16 h, 16 h + 16) of qp, u, du, dqp and s_ij: the sine columns 16 h + k and the cosine columns 32 + 16 h + k, k < 16.
+ * Summation order: every dot product over the head width (score, dA = dout . v + du . s, delta) is one partial sum per
+ * half - the bias terms first, ascending k with sine then cosine, then the row-side terms in ascending column - and the
+ * two partials are added as half0 + half1 on both lanes (exchanged in registers, v_permlane32_swap), so both hold the
+ * same bits.  delta is summed as dA: an event of one pulse has dq = dk = dqp = 0 exactly and out = v bit for bit. */
+int gn_rel_attention_wide_supported(int32_t DH);
+int gn_rel_attention_wide_fwd(const float* qkv, int64_t ld, const float* qp, int64_t ldqp, const float* xt, int64_t ldxt,
+                              const float* freq, int32_t H, int32_t DH, const int32_t* ptr, const int32_t* tile_ptr, int32_t B,
+                              int32_t N, float* out, int64_t ldo, float* u, int64_t ldu, float* lse2, void* stream);
+int gn_rel_attention_wide_bwd(const float* qkv, int64_t ld, const float* qp, int64_t ldqp, const float* xt, int64_t ldxt,
+                              const float* freq, int32_t H, int32_t DH, const int32_t* ptr, const int32_t* tile_ptr, int32_t B,
+                              int32_t N, const float* out, int64_t ldo, const float* u, int64_t ldu, const float* dout,
+                              int64_t lddo, const float* du, int64_t lddu, const float* lse2, float* delta, float* dqkv,
+                              int64_t lddq, float* dqp, int64_t lddqp, void* stream);
+
 /* ---- ragged multi-head self attention (DynTrans, models/components/layers.py:166-197) ---- */
 /* Replaces to_dense_batch + torch.nn.TransformerEncoder's attention + x[mask]: every pulse attends to the
  * pulses of its own event (ptr), nothing is padded.  qkv[N, ld] = [Q | K | V], each H*DH wide (the in_proj

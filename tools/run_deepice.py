@@ -9,7 +9,10 @@ device events, beside the plain ragged attention (fp32 and bf16 kernels) on the 
 gn_icemix_nodes call: a random 192 of each longer event, the auxiliary flag flipped) in place of the host loop that keeps the
 first 192; the default workload is the host loop, so that its numbers stay comparable with earlier ones.
 
-usage: run_deepice.py [B] [fp32|bf16] [steps] [--icemix]"""
+--head-size 64 runs the B_d64 shape instead (hidden 768, 12 heads of 64): the biased blocks on gn_rel_attention_wide_fwd /
+_bwd (two lanes per query), everything else as above.
+
+usage: run_deepice.py [B] [fp32|bf16] [steps] [--icemix] [--head-size {32,64}]"""
 import json
 import os
 import sys
@@ -25,10 +28,20 @@ from graphnet_amd.synthetic import synthetic_icecube86_raw            # noqa: E4
 
 ICEMIX = "--icemix" in sys.argv
 argv = [a for a in sys.argv if a != "--icemix"]
+HEAD = 32
+if "--head-size" in argv:
+    i = argv.index("--head-size")
+    HEAD = int(argv[i + 1])
+    del argv[i:i + 2]
+if HEAD not in (32, 64):
+    sys.exit("--head-size: 32 or 64")
+WIDE = HEAD == 64
+rel_fwd, rel_bwd = (ops.rel_attention_wide_fwd, ops.rel_attention_wide_bwd) if WIDE else (ops.rel_attention_fwd, ops.rel_attention_bwd)
+REL = "rel_attention_wide" if WIDE else "rel_attention"
 B = int(argv[1]) if len(argv) > 1 else 1024
 dtype = argv[2] if len(argv) > 2 else "bf16"
 steps = int(argv[3]) if len(argv) > 3 else 10
-MAX_PULSES, HIDDEN, HEAD = 192, 768, 32
+MAX_PULSES, HIDDEN = 192, 768
 torch.manual_seed(0)
 
 NAMES = ["x", "y", "z", "time", "charge", "auxiliary"]
@@ -72,7 +85,7 @@ def timed(fn, reps=10, warm=2):
     return a.elapsed_time(z) / reps
 
 
-# the attention kernels alone, one layer of the B_d32 shape (24 heads of 32)
+# the attention kernels alone, one layer of the B_d32 shape (24 heads of 32) or the B_d64 shape (12 heads of 64)
 H = HIDDEN // HEAD
 ptr32 = batch.ptr.to(torch.int32)
 plan = ops.attention_plan(ptr32)
@@ -80,11 +93,11 @@ qkv = torch.randn(N, 3 * HIDDEN, device="cuda")
 qp = torch.randn(N, HIDDEN, device="cuda") * 0.5
 xt = batch.x[:, :4].contiguous()
 freq = ops.rel_attention_freq(HEAD, "cuda")
-out, u, lse2 = ops.rel_attention_fwd(qkv, qp, xt, freq, H, ptr32, plan)
+out, u, lse2 = rel_fwd(qkv, qp, xt, freq, H, ptr32, plan)
 dout, du = torch.randn_like(out), torch.randn_like(u)
 pieces = {
-    "rel_attention_fwd": timed(lambda: ops.rel_attention_fwd(qkv, qp, xt, freq, H, ptr32, plan)),
-    "rel_attention_bwd": timed(lambda: ops.rel_attention_bwd(qkv, qp, xt, freq, H, ptr32, plan, out, u, lse2, dout, du)),
+    REL + "_fwd": timed(lambda: rel_fwd(qkv, qp, xt, freq, H, ptr32, plan)),
+    REL + "_bwd": timed(lambda: rel_bwd(qkv, qp, xt, freq, H, ptr32, plan, out, u, lse2, dout, du)),
 }
 o32, l32 = ops.attention_fwd(qkv, H, ptr32, plan)
 pieces["attention_fwd_fp32"] = timed(lambda: ops.attention_fwd(qkv, H, ptr32, plan))
@@ -126,18 +139,19 @@ for n_rel in (1, 4):
     ops.enable_timers(False)
     results[n_rel] = {"ms_per_step": 1e3 * dt, "events_per_s": B / dt, "loss": float(l),
                       "phase_ms_per_step": {k: ms / 3 for k, (n_, ms) in sorted(summary.items(), key=lambda kv: -kv[1][1])}}
-    print(f"DeepIce B_d32 n_rel={n_rel} B={B} {dtype}: {1e3 * dt:.2f} ms/step  {B / dt:.0f} events/s  loss {float(l):.4f}", flush=True)
+    print(f"DeepIce B_d{HEAD} n_rel={n_rel} B={B} {dtype}: {1e3 * dt:.2f} ms/step  {B / dt:.0f} events/s  loss {float(l):.4f}", flush=True)
     del m, opt
 
 peak = torch.cuda.max_memory_allocated() / 2**30
 print(json.dumps({
-    "metric": "events/sec DeepIce (B_d32 shape: hidden 768, 24 heads of 32, 4 + 12 blocks, n_rel 1) fwd+bwd+AdamW, synthetic IceCube-86",
+    "metric": f"events/sec DeepIce (B_d{HEAD} shape: hidden 768, {H} heads of {HEAD}, 4 + 12 blocks, n_rel 1) fwd+bwd+AdamW, "
+              "synthetic IceCube-86",
     "value": results[1]["events_per_s"], "unit": "events/s", "n_gpus": 1, "steps": steps, "ms_per_step": results[1]["ms_per_step"],
     "ms_per_step_n_rel4": results[4]["ms_per_step"], "dtype": dtype, "data": "synthetic",
-    "config": {"workload": "DeepIce(hidden_dim=768, head_size=32, depth=12, depth_rel=4, seq_length=192) on synthetic IceCube-86 "
+    "config": {"workload": f"DeepIce(hidden_dim=768, head_size={HEAD}, depth=12, depth_rel=4, seq_length=192) on synthetic IceCube-86 "
                            "events capped at 192 pulses", "events_per_gpu": B, "pulses_per_gpu": N, "pairs_per_gpu": pairs},
     "pieces_ms": pieces,
-    "rel_over_plain_fp32": (pieces["rel_attention_fwd"] + pieces["rel_attention_bwd"]) /
+    "rel_over_plain_fp32": (pieces[REL + "_fwd"] + pieces[REL + "_bwd"]) /
                            (pieces["attention_fwd_fp32"] + pieces["attention_bwd_fp32"]),
     "peak_mem_gib": peak,
     "phase_ms_per_step": {str(k): v["phase_ms_per_step"] for k, v in results.items()}}))
