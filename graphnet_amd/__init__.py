@@ -18,6 +18,7 @@ from .gnn import GNN, DynEdge, DynEdgeConv, DynEdgeJINST  # noqa: F401
 from .tito import DynEdgeTITO, DynTrans  # noqa: F401
 from .rnn import Node_RNN, RNN_TITO  # noqa: F401
 from .particlenet import ParticleNeT  # noqa: F401
+from .convnet import ConvNet, TAGConv  # noqa: F401
 from .icemix import (  # noqa: F401
     Attention_rel, Block, Block_rel, DeepIce, DropPath, FourierEncoder, Mlp, SinusoidalPosEmb, SpacetimeEncoder,
 )

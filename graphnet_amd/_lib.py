@@ -113,6 +113,12 @@ SIGNATURES = {
     "gn_rel_attention_wide_fwd": (I32, [P, I64, P, I64, P, I64, P, I32, I32, P, P, I32, I32, P, I64, P, I64, P, P]),
     "gn_rel_attention_wide_bwd": (I32, [P, I64, P, I64, P, I64, P, I32, I32, P, P, I32, I32, P, I64, P, I64, P, I64, P, I64, P,
                                         P, P, I64, P, I64, P]),
+    "gn_tagconv_supported": (I32, [I32, I32]),
+    "gn_tag_norm": (I32, [P, P, I32, I32, P, P]),
+    "gn_tag_propagate": (I32, [P, I64, P, P, P, I32, I32, I32, P, I64, P]),
+    "gn_tag_propagate_t": (I32, [P, I64, P, I64, P, P, P, P, P, P, I32, I32, I32, P, I64, P]),
+    "gn_tagconv_fwd": (I32, [I32, P, I64, P, I64, P, P, P, I32, I32, I32, P, P, I32, P, I64, P, I64, P]),
+    "gn_tag_dpre": (I32, [P, I64, P, I64, I64, I32, P, I64, P]),
     "gn_bn_blocks": (I64, [I64]),
     "gn_bn_sums": (I32, [I32, I32, P, I64, I64, I32, P, P, I64, P, P, P, P, P, P, P]),
     "gn_bn_finalize": (I32, [P, P, I32, c_float, P, P, P, P]),

@@ -702,6 +702,44 @@ int gn_dropout(const void* x, int64_t ldx, int32_t x_lowp, const float* res, int
 }
 
 
+// ---- TAGConv (tagconv.hip) ----
+#define GN_TAG_SHAPE "need 1<=K<=32, C%32==0, 32<=C<=256, non-null 16-byte aligned fp32 rows with pitch%4==0 and pitch>=C"
+int32_t gn_tagconv_supported(int32_t C_in, int32_t C_out) { return gn::tagconv_supported(C_in, C_out) ? 1 : 0; }
+int gn_tag_norm(const int32_t* nbr, const int32_t* ovf, int32_t N, int32_t K, float* dis, void* stream) {
+    hipError_t r = gn::launch_tag_norm(nbr, ovf, N, K, dis, S(stream));
+    if (r == hipErrorInvalidValue) return bad("gn_tag_norm", "need N>=0, 1<=K<=32, nbr[N,K] and dis[N]");
+    return fail(r, "gn_tag_norm");
+}
+int gn_tag_propagate(const float* x, int64_t ldx, const float* dis, const int32_t* nbr, const int32_t* ovf, int32_t N, int32_t K,
+                     int32_t C, float* h, int64_t ldh, void* stream) {
+    hipError_t r = gn::launch_tag_propagate(x, ldx, dis, nbr, ovf, N, K, C, h, ldh, S(stream));
+    if (r == hipErrorInvalidValue) return bad("gn_tag_propagate", GN_TAG_SHAPE);
+    return fail(r, "gn_tag_propagate");
+}
+int gn_tag_propagate_t(const float* g, int64_t ldg, const float* add, int64_t ldadd, const float* dis, const int32_t* rev_ptr,
+                       const int32_t* rev_rows, const int32_t* hubs, const int32_t* nhubs, const int32_t* ovf_centre, int32_t N,
+                       int32_t K, int32_t C, float* out, int64_t ldo, void* stream) {
+    hipError_t r = gn::launch_tag_propagate_t(g, ldg, add, ldadd, dis, rev_ptr, rev_rows, hubs, nhubs, ovf_centre, N, K, C, out, ldo,
+                                              S(stream));
+    if (r == hipErrorInvalidValue) return bad("gn_tag_propagate_t", GN_TAG_SHAPE ", the reverse lists with their hub list");
+    return fail(r, "gn_tag_propagate_t");
+}
+int gn_tagconv_fwd(int32_t mode, const float* x, int64_t ldx, const float* h1, int64_t ldh1, const float* dis, const int32_t* nbr,
+                   const int32_t* ovf, int32_t N, int32_t K, int32_t C_in, const void* Wp, const float* bias, int32_t C_out,
+                   float* h2, int64_t ldh2, float* out, int64_t ldo, void* stream) {
+    hipError_t r = gn::launch_tagconv_fwd(mode, x, ldx, h1, ldh1, dis, nbr, ovf, N, K, C_in, Wp, bias, C_out, h2, ldh2, out, ldo,
+                                          S(stream));
+    if (r == hipErrorInvalidValue) return bad("gn_tagconv_fwd", GN_TAG_SHAPE " (C_in and C_out), mode 0 / 1, packed weights");
+    return fail(r, "gn_tagconv_fwd");
+}
+int gn_tag_dpre(const float* dout, int64_t lddo, const float* out, int64_t ldo, int64_t N, int32_t C, float* dpre, int64_t ldp,
+                void* stream) {
+    hipError_t r = gn::launch_tag_dpre(dout, lddo, out, ldo, N, C, dpre, ldp, S(stream));
+    if (r == hipErrorInvalidValue) return bad("gn_tag_dpre", "need C%4==0, non-null 16-byte aligned fp32 rows with pitch%4==0 and pitch>=C");
+    return fail(r, "gn_tag_dpre");
+}
+#undef GN_TAG_SHAPE
+
 int64_t gn_bn_blocks(int64_t rows) { return gn::bn_blocks(rows); }
 int gn_bn_sums(int32_t mode, int32_t act, const float* z, int64_t ldz, int64_t rows, int32_t C, const int32_t* valid,
                const float* g, int64_t ldg, const float* mean, const float* rstd, const float* gamma, const float* beta,

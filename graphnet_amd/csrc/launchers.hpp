@@ -194,6 +194,19 @@ hipError_t launch_rel_attn_wide_bwd(const float* qkv, long long ld, const float*
                                     int N, const float* out, long long ldo, const float* u, long long ldu, const float* dout,
                                     long long lddo, const float* du, long long lddu, const float* lse2, float* delta,
                                     float* dqkv, long long lddq, float* dqp, long long lddqp, hipStream_t st);
+// tagconv.hip: TAGConv(K = 2) - normalised-adjacency propagation, its transpose and the fused layer (fp32 rows, widths % 32, <= 256)
+bool tagconv_supported(int C_in, int C_out);
+hipError_t launch_tag_norm(const int* nbr, const int* ovf, int N, int K, float* dis, hipStream_t st);
+hipError_t launch_tag_propagate(const float* x, long long ldx, const float* dis, const int* nbr, const int* ovf, int N, int K, int C,
+                                float* h, long long ldh, hipStream_t st);
+hipError_t launch_tag_propagate_t(const float* g, long long ldg, const float* add, long long lda, const float* dis,
+                                  const int* rev_ptr, const int* rev_rows, const int* hubs, const int* nhubs, const int* ovf_centre,
+                                  int N, int K, int C, float* out, long long ldo, hipStream_t st);
+hipError_t launch_tagconv_fwd(int mode, const float* x, long long ldx, const float* h1, long long ldh1, const float* dis,
+                              const int* nbr, const int* ovf, int N, int K, int C_in, const void* Wp, const float* bias, int C_out,
+                              float* h2, long long ldh2, float* out, long long ldo, hipStream_t st);
+hipError_t launch_tag_dpre(const float* dout, long long lddo, const float* out, long long ldo, long long N, int C, float* dpre,
+                           long long ldp, hipStream_t st);
 // generic.hip: dropout (+ residual add); thresh = round(p * 2^32)
 hipError_t launch_dropout(const void* x, long long ldx, int x_lowp, const float* res, long long ldres, void* y, long long ldy,
                           int y_lowp, long long rows, int cols, unsigned seed, unsigned thresh, hipStream_t st);

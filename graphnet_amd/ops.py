@@ -1399,3 +1399,83 @@ def rel_attention_wide_bwd(qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_
                            out: Tensor, u: Tensor, lse2: Tensor, dout: Tensor, du: Tensor) -> Tuple[Tensor, Tensor]:
     """Gradients of :func:`rel_attention_wide_fwd` (``gn_rel_attention_wide_bwd``) -> (dqkv ``[N, 3 d]``, dqp ``[N, d]``)."""
     return _rel_bwd(qkv, qp, xt, freq, n_head, ptr, plan, out, u, lse2, dout, du, True)
+
+
+# ------------------------------------------------------------------------------ TAGConv (ConvNet)
+def tagconv_supported(C_in: int, C_out: int) -> bool:
+    """Widths the TAGConv kernels take: multiples of 32 in [32, 256] (``gn_tagconv_supported``)."""
+    return bool(_lib.lib().gn_tagconv_supported(int(C_in), int(C_out)))
+
+
+def _tag_rows(t: Tensor, C: int, name: str) -> int:
+    _need(t, torch.float32, name)
+    if int(t.shape[1]) < C:
+        raise ValueError(f"{name}: need at least {C} columns")
+    return _rows(t, name)
+
+
+def tag_norm(g: NeighbourTable) -> Tensor:
+    """``dis[N] = deg^-1/2`` (0 where ``deg == 0``) of the table's in-degrees: ``gcn_norm`` without self loops."""
+    dis = torch.empty(max(g.N, 1), dtype=torch.float32, device=g.nbr.device)[:g.N]
+    with _timed("tag_norm"):
+        _lib.check(_lib.lib().gn_tag_norm(_p(g.nbr), _p(g.ovf), g.N, g.K, _p(dis), _st()))
+    return dis
+
+
+def tag_propagate(x: Tensor, C: int, g: NeighbourTable, dis: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """``h[N, C] = P x`` with ``(P x)_i = dis[i] * sum_{j -> i} dis[j] x_j`` (slot order, then the overflow entry)."""
+    ldx = _tag_rows(x, C, "x")
+    _need(dis, torch.float32, "dis")
+    if out is None:
+        out = torch.empty((g.N, C), dtype=torch.float32, device=x.device)
+    with _timed("tag_propagate"):
+        _lib.check(_lib.lib().gn_tag_propagate(_p(x), ldx, _p(dis), _p(g.nbr), _p(g.ovf), g.N, g.K, C, _p(out),
+                                               _tag_rows(out, C, "out"), _st()))
+    return out
+
+
+def tag_propagate_t(gr: Tensor, C: int, g: NeighbourTable, dis: Tensor, add: Optional[Tensor] = None,
+                    out: Optional[Tensor] = None) -> Tensor:
+    """``out[N, C] = add + P^T gr`` over the table's reverse lists (built on first use); fixed summation order."""
+    g.build_reverse()
+    ldg = _tag_rows(gr, C, "g")
+    _need(dis, torch.float32, "dis")
+    if out is None:
+        out = torch.empty((g.N, C), dtype=torch.float32, device=gr.device)
+    with _timed("tag_propagate_t"):
+        _lib.check(_lib.lib().gn_tag_propagate_t(_p(gr), ldg, _p(add), 0 if add is None else _tag_rows(add, C, "add"), _p(dis),
+                                                 _p(g.rev_ptr), _p(g.rev_rows), _p(g.rev_hubs), _p(g.rev_nhubs),
+                                                 _p(g.ovf_centre), g.N, g.K, C, _p(out), _tag_rows(out, C, "out"), _st()))
+    return out
+
+
+def tagconv_pack(weights: Sequence[Tensor], mode: int) -> Tensor:
+    """``[W0 | W1 | W2]`` as the operand ``gn_tagconv_fwd`` reads: ``[C_out][3 C_in]`` in the mode's compute type."""
+    return torch.cat([w.detach() for w in weights], dim=1).to(mode_dtype(mode)).contiguous()
+
+
+def tagconv_fwd(mode: int, x: Tensor, h1: Tensor, g: NeighbourTable, dis: Tensor, Wp: Tensor, bias: Optional[Tensor],
+                C_in: int, C_out: int) -> Tuple[Tensor, Tensor]:
+    """One fused layer: ``h2 = P h1`` and ``out = leaky_relu([x | h1 | h2] Wp^T + bias, 0.01)`` -> ``(out, h2)``."""
+    _need(Wp, mode_dtype(mode), "Wp")
+    if tuple(Wp.shape) != (C_out, 3 * C_in) or not Wp.is_contiguous():
+        raise ValueError(f"Wp: need a contiguous [{C_out}, {3 * C_in}] operand (tagconv_pack)")
+    if bias is not None:
+        _need(bias, torch.float32, "bias")
+    _need(dis, torch.float32, "dis")
+    h2 = torch.empty((g.N, C_in), dtype=torch.float32, device=x.device)
+    out = torch.empty((g.N, C_out), dtype=torch.float32, device=x.device)
+    with _timed("tagconv_fwd", f"tagconv_fwd[{C_in}x{C_out}]"):
+        _lib.check(_lib.lib().gn_tagconv_fwd(mode, _p(x), _tag_rows(x, C_in, "x"), _p(h1), _tag_rows(h1, C_in, "h1"), _p(dis),
+                                             _p(g.nbr), _p(g.ovf), g.N, g.K, C_in, _p(Wp), _p(bias), C_out, _p(h2), C_in,
+                                             _p(out), C_out, _st()))
+    return out, h2
+
+
+def tag_dpre(dout: Tensor, out: Tensor, C: int) -> Tensor:
+    """``dpre = dout * (out > 0 ? 1 : 0.01)``: the leaky-ReLU backward from the sign of the layer's output."""
+    dpre = torch.empty((int(out.shape[0]), C), dtype=torch.float32, device=out.device)
+    with _timed("tag_dpre"):
+        _lib.check(_lib.lib().gn_tag_dpre(_p(dout), _tag_rows(dout, C, "dout"), _p(out), _tag_rows(out, C, "out"),
+                                          int(out.shape[0]), C, _p(dpre), C, _st()))
+    return dpre

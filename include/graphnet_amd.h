@@ -509,6 +509,36 @@ int gn_segment_pool_bwd(const float* gout, int32_t C, const int32_t* ptr, const 
                         const float* gate, int64_t ldgate, void* dx, int64_t lddx, int32_t dx_lowp, void* stream);
 /* (dx: fp32, or bf16 when dx_lowp) */
 
+/* ---- TAGConv(K = 2) of ConvNet (torch_geometric.nn.TAGConv via models/gnn/convnet.py:44-46) ---------------
+ * Propagation with the symmetrically normalised adjacency of the neighbour table (gcn_norm without self loops):
+ *   deg[i]  = valid entries of table row i (nbr[i, 0..K) >= 0, plus ovf[i] >= 0 when ovf != NULL)
+ *   dis[i]  = deg[i] > 0 ? deg[i]^-1/2 : 0
+ *   (P x)_i = dis[i] * sum_{j -> i} dis[j] * x_j        fp32, slots 0..K-1 in order, then the overflow entry
+ * All rows are fp32 with pitches (elements) that are multiples of 4 and 16-byte aligned bases; widths C are multiples of
+ * 32 in [32, 256] (gn_tagconv_supported), 1 <= K <= 32.  No atomics: every entry is bit-repeatable. */
+int32_t gn_tagconv_supported(int32_t C_in, int32_t C_out);
+/* dis[N] from the table; ovf: per-centre overflow source ([N], -1 = none) or NULL */
+int gn_tag_norm(const int32_t* nbr, const int32_t* ovf, int32_t N, int32_t K, float* dis, void* stream);
+/* h[N, C] = P x */
+int gn_tag_propagate(const float* x, int64_t ldx, const float* dis, const int32_t* nbr, const int32_t* ovf, int32_t N, int32_t K,
+                     int32_t C, float* h, int64_t ldh, void* stream);
+/* out[N, C] = add + P^T g (add may be NULL) over the reverse lists of gn_rev_build* (rows in ascending id per node; hubs /
+ * nhubs: the hub list the build leaves behind, required - those nodes are summed by a 16-wave workgroup each in a fixed
+ * block order); ovf_centre: centre of every overflow row (gn_ovf_compact), NULL for a table without overflow rows. */
+int gn_tag_propagate_t(const float* g, int64_t ldg, const float* add, int64_t ldadd, const float* dis, const int32_t* rev_ptr,
+                       const int32_t* rev_rows, const int32_t* hubs, const int32_t* nhubs, const int32_t* ovf_centre, int32_t N,
+                       int32_t K, int32_t C, float* out, int64_t ldo, void* stream);
+/* One layer: h2 = P h1 (written, the weight gradient reads it) and
+ *   out[N, C_out] = leaky_relu([x | h1 | h2] . Wp^T + bias, 0.01),   Wp = [W0 | W1 | W2]: T[C_out][3*C_in], row-major, unpadded,
+ * T = float (mode 0: v_mfma_f32_32x32x2_f32) or bf16 (mode 1: the A operand is rounded to bf16 as it is staged;
+ * fp32 accumulation).  bias[C_out] may be NULL.  The pre-activation is not stored: its sign is the sign of out. */
+int gn_tagconv_fwd(int32_t mode, const float* x, int64_t ldx, const float* h1, int64_t ldh1, const float* dis, const int32_t* nbr,
+                   const int32_t* ovf, int32_t N, int32_t K, int32_t C_in, const void* Wp, const float* bias, int32_t C_out,
+                   float* h2, int64_t ldh2, float* out, int64_t ldo, void* stream);
+/* dpre[N, C] = dout * (out > 0 ? 1 : 0.01); C a multiple of 4 */
+int gn_tag_dpre(const float* dout, int64_t lddo, const float* out, int64_t ldo, int64_t N, int32_t C, float* dpre, int64_t ldp,
+                void* stream);
+
 /* ---- ragged attention with the spacetime bias of DeepIce (models/components/layers.py:389-499, embedding.py:139-175) ---- */
 /* Attention_rel without the [B, L, L, dh] bias tensor.  With s_ij the sinusoidal embedding (width DH) of the clipped
  * 4-distance of pulses i, j of one event and R_ij = W s_ij + b its projection, the reference's scores and outputs are
