@@ -5,7 +5,8 @@ constructor signatures, defaults and sub-module names, hence the same state-dict
 ``[B, L, d]``, materialises the spacetime bias as ``[B, L, L, head_size]`` fp32 and contracts it twice per layer.  Here the
 batch stays ragged (``x``, ``ptr``) and neither tensor exists:
 
-* blocks with the spacetime bias run on ``csrc/attn_rel.hip`` (head width 32) or ``csrc/attn_rel_wide.hip`` (64).
+* blocks with the spacetime bias run on ``csrc/attn_rel.hip`` (head width 32; with ``Attention_rel.shared_bias`` on
+  ``csrc/attn_rel_shared.hip``) or ``csrc/attn_rel_wide.hip`` (64).
   With ``s_ij`` the sinusoidal embedding of the clipped 4-distance and ``R_ij = W s_ij + b`` (``rel_pos.projection``), ``q~ . k + q~ . R_ij = q~ . k + (W^T q~) . s_ij + const`` and
   ``sum_j a_ij (v_j + R_ij) = O_i + W U_i + b`` with ``U_i = sum_j a_ij s_ij``: the kernel takes ``q, k, v`` and ``q' = W^T q~``,
   recomputes ``s_ij`` per pair and returns ``O`` and ``U``; ``W`` and ``b`` stay in two small GEMMs with plain autograd;
@@ -49,26 +50,32 @@ class _RaggedAttentionFunction(torch.autograd.Function):
 
 
 class _RelAttentionFunction(torch.autograd.Function):
-    """Ragged attention with the spacetime bias recomputed per pair (``ops.rel_attention_fwd`` / ``rel_attention_bwd``, at
-    head width 64 ``ops.rel_attention_wide_fwd`` / ``rel_attention_wide_bwd``): (qkv ``[N, 3 d]``, qp ``[N, d]``) -> (out, u),
-    both ``[N, d]``; ``xt`` and ``freq`` are data."""
+    """Ragged attention with the spacetime bias recomputed per pair: (qkv ``[N, 3 d]``, qp ``[N, d]``) -> (out, u), both
+    ``[N, d]``; ``xt`` and ``freq`` are data.  Head width 64 runs on ``ops.rel_attention_wide_*``, head width 32 on
+    ``ops.rel_attention_*`` or, with ``shared`` (``Attention_rel.shared_bias``), on ``ops.rel_attention_shared_*``."""
 
     @staticmethod
-    def forward(ctx, qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, ptr: Tensor, plan: Tensor):  # type: ignore[override]
+    def forward(ctx, qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, ptr: Tensor, plan: Tensor,
+                shared: bool = False):  # type: ignore[override]
         qkv, qp = qkv.contiguous(), qp.contiguous()
-        wide = ops.rel_attention_wide_supported(int(qp.shape[1]) // n_head)
-        out, u, lse2 = (ops.rel_attention_wide_fwd if wide else ops.rel_attention_fwd)(qkv, qp, xt, freq, n_head, ptr, plan)
+        dh = int(qp.shape[1]) // n_head
+        if ops.rel_attention_wide_supported(dh):
+            fwd, ctx.bwd = ops.rel_attention_wide_fwd, ops.rel_attention_wide_bwd
+        elif shared and ops.rel_attention_shared_supported(dh):
+            fwd, ctx.bwd = ops.rel_attention_shared_fwd, ops.rel_attention_shared_bwd
+        else:
+            fwd, ctx.bwd = ops.rel_attention_fwd, ops.rel_attention_bwd
+        out, u, lse2 = fwd(qkv, qp, xt, freq, n_head, ptr, plan)
         ctx.save_for_backward(qkv, qp, xt, freq, ptr, plan, out, u, lse2)
-        ctx.n_head, ctx.wide = n_head, wide
+        ctx.n_head = n_head
         return out, u
 
     @staticmethod
     def backward(ctx, dout: Tensor, du: Tensor):  # type: ignore[override]
         qkv, qp, xt, freq, ptr, plan, out, u, lse2 = ctx.saved_tensors
-        bwd = ops.rel_attention_wide_bwd if ctx.wide else ops.rel_attention_bwd
-        dqkv, dqp = bwd(qkv, qp, xt, freq, ctx.n_head, ptr, plan, out, u, lse2, dout.contiguous().to(torch.float32),
-                        du.contiguous().to(torch.float32))
-        return dqkv, dqp, None, None, None, None, None
+        dqkv, dqp = ctx.bwd(qkv, qp, xt, freq, ctx.n_head, ptr, plan, out, u, lse2, dout.contiguous().to(torch.float32),
+                            du.contiguous().to(torch.float32))
+        return dqkv, dqp, None, None, None, None, None, None
 
 
 def _rel_width_built(dh: int) -> bool:
@@ -215,7 +222,13 @@ def _plain_attention(qkv: Tensor, n_head: int, cfg: Dict[str, Any]) -> Tensor:
 class Attention_rel(Model):
     """``layers.py:389-499`` on ragged rows.  ``forward(x [N, d], cfg, rel)``: ``rel`` is the ``SpacetimeEncoder`` whose bias
     the scores and values take, or None for plain attention; ``cfg`` holds ``ptr`` (int32), ``plan``, ``mode`` and, for the
-    bias, ``xt`` ``[N, >= 4]`` (x, y, z, time) and ``freq``."""
+    bias, ``xt`` ``[N, >= 4]`` (x, y, z, time) and ``freq``.
+
+    ``shared_bias`` (a class attribute, so that the reference's constructor signature stays): at head width 32 run the
+    biased attention on the kernels that form each pair's ``s_ij`` once for 8 heads (``csrc/attn_rel_shared.hip``) instead of
+    once per head; the same results bit for bit.  Off by default."""
+
+    shared_bias = False
 
     def __init__(self, input_dim: int, num_heads: int = 8, qkv_bias: bool = False, qk_scale: Optional[float] = None,
                  attn_drop: float = 0.0, proj_drop: float = 0.0, attn_head_dim: Optional[int] = None):
@@ -263,7 +276,7 @@ class Attention_rel(Model):
             qkv = qkv.to(torch.float32)
             Wr, br = rel.projection.weight, rel.projection.bias                  # R_ij = Wr s_ij + br
             qp = torch.matmul(qkv[:, :d].reshape(N, H, dh) * self.scale, Wr).reshape(N, d)      # W^T q~ per head
-            out, u = _RelAttentionFunction.apply(qkv, qp, cfg["xt"], cfg["freq"], H, cfg["ptr"], cfg["plan"])
+            out, u = _RelAttentionFunction.apply(qkv, qp, cfg["xt"], cfg["freq"], H, cfg["ptr"], cfg["plan"], self.shared_bias)
             att = (out.reshape(N, H, dh) + torch.matmul(u.reshape(N, H, dh), Wr.t()) + br).reshape(N, d)
         return _linear(att, self.proj.weight, self.proj.bias, mode).to(torch.float32)
 

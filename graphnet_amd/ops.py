@@ -1329,28 +1329,41 @@ def rel_attention_wide_supported(dh: int) -> bool:
     return bool(_lib.lib().gn_rel_attention_wide_supported(int(dh)))
 
 
-def _rel_check(qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, wide: bool = False) -> Tuple[int, int]:
+def rel_attention_shared_supported(dh: int) -> bool:
+    """Head widths of the biased attention kernels that form ``s_ij`` once per pair for a group of heads
+    (``gn_rel_attention_shared_supported``): 32."""
+    return bool(_lib.lib().gn_rel_attention_shared_supported(int(dh)))
+
+
+_REL_FAMILY = {            # kernel family (the stem of its C entries) -> (what the message calls it, the head width it is built for)
+    "rel_attention": ("", 32),
+    "rel_attention_wide": (" (two lanes per query)", 64),
+    "rel_attention_shared": (" (s_ij shared by a group of heads)", 32),
+}
+
+
+def _rel_check(qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, family: str) -> Tuple[int, int]:
     for t, name in ((qkv, "qkv"), (qp, "qp"), (xt, "xt"), (freq, "freq")):
         _need(t, torch.float32, name)
     N, d = int(qp.shape[0]), int(qp.shape[1])
     if int(qkv.shape[0]) != N or int(qkv.shape[1]) != 3 * d or d % n_head or int(xt.shape[0]) != N or int(xt.shape[1]) < 4:
         raise ValueError("need qkv [N, 3*d], qp [N, d] with d a multiple of the number of heads, xt [N, >= 4]")
     dh = d // n_head
-    if not (rel_attention_wide_supported(dh) if wide else rel_attention_supported(dh)):
-        raise NotImplementedError(f"biased ragged attention{' (two lanes per query)' if wide else ''}: head width {dh} is not "
-                                  f"built ({64 if wide else 32} is); no fallback")
+    what, built = _REL_FAMILY[family]
+    if not getattr(_lib.lib(), f"gn_{family}_supported")(dh):
+        raise NotImplementedError(f"biased ragged attention{what}: head width {dh} is not built ({built} is); no fallback")
     if int(freq.numel()) != dh // 2 or not freq.is_contiguous():
         raise ValueError("freq must hold dh / 2 contiguous frequencies")
     return N, d
 
 
-def _rel_fwd(qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, ptr: Tensor, plan: Tensor, wide: bool):
-    N, d = _rel_check(qkv, qp, xt, freq, n_head, wide)
+def _rel_fwd(qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, ptr: Tensor, plan: Tensor, family: str):
+    N, d = _rel_check(qkv, qp, xt, freq, n_head, family)
     B = int(ptr.shape[0]) - 1
     out = torch.empty((N, d), dtype=torch.float32, device=qkv.device)
     u = torch.empty((N, d), dtype=torch.float32, device=qkv.device)
     lse2 = torch.empty((N, n_head), dtype=torch.float32, device=qkv.device)
-    name = "rel_attention_wide_fwd" if wide else "rel_attention_fwd"
+    name = family + "_fwd"
     with _timed(name):
         _lib.check(getattr(_lib.lib(), "gn_" + name)(_p(qkv), _rows(qkv, "qkv"), _p(qp), _rows(qp, "qp"), _p(xt), _rows(xt, "xt"),
                                                      _p(freq), n_head, d // n_head, _p(ptr), _p(plan), B, N, _p(out), d, _p(u), d,
@@ -1359,15 +1372,15 @@ def _rel_fwd(qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, ptr
 
 
 def _rel_bwd(qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, ptr: Tensor, plan: Tensor, out: Tensor, u: Tensor,
-             lse2: Tensor, dout: Tensor, du: Tensor, wide: bool) -> Tuple[Tensor, Tensor]:
-    N, d = _rel_check(qkv, qp, xt, freq, n_head, wide)
+             lse2: Tensor, dout: Tensor, du: Tensor, family: str) -> Tuple[Tensor, Tensor]:
+    N, d = _rel_check(qkv, qp, xt, freq, n_head, family)
     for t, name in ((out, "out"), (u, "u"), (dout, "dout"), (du, "du"), (lse2, "lse2")):
         _need(t, torch.float32, name)
     B = int(ptr.shape[0]) - 1
     dqkv = torch.empty((N, 3 * d), dtype=torch.float32, device=qkv.device)
     dqp = torch.empty((N, d), dtype=torch.float32, device=qkv.device)
     delta = torch.empty((N, n_head), dtype=torch.float32, device=qkv.device)
-    name = "rel_attention_wide_bwd" if wide else "rel_attention_bwd"
+    name = family + "_bwd"
     with _timed(name):
         _lib.check(getattr(_lib.lib(), "gn_" + name)(_p(qkv), _rows(qkv, "qkv"), _p(qp), _rows(qp, "qp"), _p(xt), _rows(xt, "xt"),
                                                      _p(freq), n_head, d // n_head, _p(ptr), _p(plan), B, N, _p(out),
@@ -1381,24 +1394,36 @@ def rel_attention_fwd(qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head:
     """Ragged attention with the spacetime bias of ``DeepIce`` recomputed per pair (``gn_rel_attention_fwd``): scores
     ``q k / sqrt(dh) + qp . s_ij``, ``s_ij`` the sinusoidal embedding of the clipped 4-distance of pulses ``i``, ``j`` (columns
     0-3 of ``xt``: x, y, z, time).  fp32.  -> (out ``[N, d]`` = sum_j a_ij v_j, u ``[N, d]`` = sum_j a_ij s_ij, lse2 ``[N, H]``)."""
-    return _rel_fwd(qkv, qp, xt, freq, n_head, ptr, plan, False)
+    return _rel_fwd(qkv, qp, xt, freq, n_head, ptr, plan, "rel_attention")
 
 
 def rel_attention_bwd(qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, ptr: Tensor, plan: Tensor,
                       out: Tensor, u: Tensor, lse2: Tensor, dout: Tensor, du: Tensor) -> Tuple[Tensor, Tensor]:
     """Gradients of :func:`rel_attention_fwd` -> (dqkv ``[N, 3 d]``, dqp ``[N, d]``); ``xt`` carries none."""
-    return _rel_bwd(qkv, qp, xt, freq, n_head, ptr, plan, out, u, lse2, dout, du, False)
+    return _rel_bwd(qkv, qp, xt, freq, n_head, ptr, plan, out, u, lse2, dout, du, "rel_attention")
 
 
 def rel_attention_wide_fwd(qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, ptr: Tensor, plan: Tensor):
     """:func:`rel_attention_fwd` for head width 64 (``gn_rel_attention_wide_fwd``: two lanes hold one query)."""
-    return _rel_fwd(qkv, qp, xt, freq, n_head, ptr, plan, True)
+    return _rel_fwd(qkv, qp, xt, freq, n_head, ptr, plan, "rel_attention_wide")
 
 
 def rel_attention_wide_bwd(qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, ptr: Tensor, plan: Tensor,
                            out: Tensor, u: Tensor, lse2: Tensor, dout: Tensor, du: Tensor) -> Tuple[Tensor, Tensor]:
     """Gradients of :func:`rel_attention_wide_fwd` (``gn_rel_attention_wide_bwd``) -> (dqkv ``[N, 3 d]``, dqp ``[N, d]``)."""
-    return _rel_bwd(qkv, qp, xt, freq, n_head, ptr, plan, out, u, lse2, dout, du, True)
+    return _rel_bwd(qkv, qp, xt, freq, n_head, ptr, plan, out, u, lse2, dout, du, "rel_attention_wide")
+
+
+def rel_attention_shared_fwd(qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, ptr: Tensor, plan: Tensor):
+    """:func:`rel_attention_fwd` (head width 32, the same bits) on ``gn_rel_attention_shared_fwd``: one workgroup serves 8 heads
+    and evaluates each pair's ``s_ij`` once for all of them."""
+    return _rel_fwd(qkv, qp, xt, freq, n_head, ptr, plan, "rel_attention_shared")
+
+
+def rel_attention_shared_bwd(qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, ptr: Tensor, plan: Tensor,
+                             out: Tensor, u: Tensor, lse2: Tensor, dout: Tensor, du: Tensor) -> Tuple[Tensor, Tensor]:
+    """Gradients of :func:`rel_attention_shared_fwd` (``gn_rel_attention_shared_bwd``) -> (dqkv ``[N, 3 d]``, dqp ``[N, d]``)."""
+    return _rel_bwd(qkv, qp, xt, freq, n_head, ptr, plan, out, u, lse2, dout, du, "rel_attention_shared")
 
 
 # ------------------------------------------------------------------------------ TAGConv (ConvNet)

@@ -12,7 +12,10 @@ first 192; the default workload is the host loop, so that its numbers stay compa
 --head-size 64 runs the B_d64 shape instead (hidden 768, 12 heads of 64): the biased blocks on gn_rel_attention_wide_fwd /
 _bwd (two lanes per query), everything else as above.
 
-usage: run_deepice.py [B] [fp32|bf16] [steps] [--icemix] [--head-size {32,64}]"""
+--shared-bias (head size 32) times the per-head kernels and the ones that form s_ij once for 8 heads (gn_rel_attention_shared_fwd /
+_bwd) on the same batch, and runs the training steps with Attention_rel.shared_bias set.
+
+usage: run_deepice.py [B] [fp32|bf16] [steps] [--icemix] [--head-size {32,64}] [--shared-bias]"""
 import json
 import os
 import sys
@@ -27,7 +30,8 @@ from graphnet_amd import ops                                          # noqa: E4
 from graphnet_amd.synthetic import synthetic_icecube86_raw            # noqa: E402
 
 ICEMIX = "--icemix" in sys.argv
-argv = [a for a in sys.argv if a != "--icemix"]
+SHARED = "--shared-bias" in sys.argv
+argv = [a for a in sys.argv if a not in ("--icemix", "--shared-bias")]
 HEAD = 32
 if "--head-size" in argv:
     i = argv.index("--head-size")
@@ -36,6 +40,9 @@ if "--head-size" in argv:
 if HEAD not in (32, 64):
     sys.exit("--head-size: 32 or 64")
 WIDE = HEAD == 64
+if SHARED and WIDE:
+    sys.exit("--shared-bias: head size 32 only")
+g.Attention_rel.shared_bias = SHARED
 rel_fwd, rel_bwd = (ops.rel_attention_wide_fwd, ops.rel_attention_wide_bwd) if WIDE else (ops.rel_attention_fwd, ops.rel_attention_bwd)
 REL = "rel_attention_wide" if WIDE else "rel_attention"
 B = int(argv[1]) if len(argv) > 1 else 1024
@@ -99,6 +106,10 @@ pieces = {
     REL + "_fwd": timed(lambda: rel_fwd(qkv, qp, xt, freq, H, ptr32, plan)),
     REL + "_bwd": timed(lambda: rel_bwd(qkv, qp, xt, freq, H, ptr32, plan, out, u, lse2, dout, du)),
 }
+if SHARED:
+    pieces["rel_attention_shared_fwd"] = timed(lambda: ops.rel_attention_shared_fwd(qkv, qp, xt, freq, H, ptr32, plan))
+    pieces["rel_attention_shared_bwd"] = timed(lambda: ops.rel_attention_shared_bwd(qkv, qp, xt, freq, H, ptr32, plan, out, u, lse2,
+                                                                                   dout, du))
 o32, l32 = ops.attention_fwd(qkv, H, ptr32, plan)
 pieces["attention_fwd_fp32"] = timed(lambda: ops.attention_fwd(qkv, H, ptr32, plan))
 pieces["attention_bwd_fp32"] = timed(lambda: ops.attention_bwd(qkv, H, ptr32, plan, o32, l32, dout))
@@ -146,7 +157,7 @@ peak = torch.cuda.max_memory_allocated() / 2**30
 print(json.dumps({
     "metric": f"events/sec DeepIce (B_d{HEAD} shape: hidden 768, {H} heads of {HEAD}, 4 + 12 blocks, n_rel 1) fwd+bwd+AdamW, "
               "synthetic IceCube-86",
-    "value": results[1]["events_per_s"], "unit": "events/s", "n_gpus": 1, "steps": steps, "ms_per_step": results[1]["ms_per_step"],
+    "value": results[1]["events_per_s"], "unit": "events/s", "n_gpus": 1, "shared_bias": SHARED, "steps": steps, "ms_per_step": results[1]["ms_per_step"],
     "ms_per_step_n_rel4": results[4]["ms_per_step"], "dtype": dtype, "data": "synthetic",
     "config": {"workload": f"DeepIce(hidden_dim=768, head_size={HEAD}, depth=12, depth_rel=4, seq_length=192) on synthetic IceCube-86 "
                            "events capped at 192 pulses", "events_per_gpu": B, "pulses_per_gpu": N, "pairs_per_gpu": pairs},
