@@ -90,6 +90,12 @@ SIGNATURES = {
     "gn_rows_compact": (I32, [P, P, I32, I32, P, P, P, P, P, P]),
     "gn_segment_rows_sum": (I32, [P, I64, I32, I32, P, P, I64, I32, P]),
     "gn_rev_rows_compact": (I32, [P, P, I32, I32, P, P, P, P, P]),
+    "gn_edgeconv_norm_supported": (I32, [I32, I32, I32]),
+    "gn_edgeconv_norm_tiles": (I32, [I32, I32]),
+    "gn_edgeconv_norm_plan": (I32, [P, I32, I32, P, P]),
+    "gn_edgeconv_norm_fwd": (I32, [I32, P, I32, I32, I32, P, P, P, I32, P, P, P, P, P, P, c_float, P, I64, P, P]),
+    "gn_edgeconv_norm_bwd": (I32, [I32, P, I32, I32, I32, P, P, P, I32, P, P, P, P, P, P, P, P, P, I64, I32, I64, P, P, P, P, I64, P,
+                                   P]),
     "gn_edge_gather_pre": (I32, [P, I32, P, P, I64, I32, P, I32, P]),
     "gn_rownorm_act_fwd": (I32, [P, I64, I32, P, P, P, c_float, I32, P, I64, I32, P, I64, P, I64, I32, P]),
     "gn_rownorm_bwd_blocks": (I32, [I64]),

@@ -502,6 +502,38 @@ int gn_segment_rows_sum(const float* m, int64_t ldm, int32_t C, int32_t N, const
     if (r == hipErrorInvalidValue) return bad("gn_segment_rows_sum", "need C >= 1");
     return fail(r, "gn_segment_rows_sum");
 }
+int32_t gn_edgeconv_norm_supported(int32_t mode, int32_t H1, int32_t H2) { return gn::edgeconv_norm_supported(mode, H1, H2) ? 1 : 0; }
+int32_t gn_edgeconv_norm_tiles(int32_t N, int32_t K) { return gn::edgeconv_norm_tiles(N, K); }
+int gn_edgeconv_norm_plan(const int32_t* row_ptr, int32_t N, int32_t K, int32_t* plan, void* stream) {
+    hipError_t r = gn::launch_edgeconv_norm_plan(row_ptr, N, K, plan, S(stream));
+    if (r == hipErrorInvalidValue) return bad("gn_edgeconv_norm_plan", "need N>=0, 1<=K<=32, row_ptr and plan");
+    return fail(r, "gn_edgeconv_norm_plan");
+}
+int gn_edgeconv_norm_fwd(int32_t mode, const float* PQ, int32_t H1p, int32_t H1, int32_t H2, const int32_t* row_ptr,
+                         const int32_t* jc, const int32_t* plan, int32_t tiles, const void* W2p, const float* b2,
+                         const float* gamma1, const float* beta1, const float* gamma2, const float* beta2, float eps,
+                         float* out, int64_t ldo, float* stats, void* stream) {
+    if (!PQ || !row_ptr || !jc || !plan || !W2p || !b2 || !gamma1 || !beta1 || !gamma2 || !beta2 || !out || !stats)
+        return bad("gn_edgeconv_norm_fwd", "null argument");
+    hipError_t r = gn::launch_edgeconv_norm_fwd(mode, PQ, H1p, H1, H2, row_ptr, jc, plan, tiles, W2p, b2, gamma1, beta1, gamma2, beta2,
+                                                eps, out, ldo, stats, S(stream));
+    if (r == hipErrorInvalidValue) return bad("gn_edgeconv_norm_fwd", "outside gn_edgeconv_norm_supported, or H1p != ceil32(H1), ldo < H2");
+    return fail(r, "gn_edgeconv_norm_fwd");
+}
+int gn_edgeconv_norm_bwd(int32_t mode, const float* PQ, int32_t H1p, int32_t H1, int32_t H2, const int32_t* row_ptr,
+                         const int32_t* jc, const int32_t* plan, int32_t tiles, const void* W2p, const void* W2Tp,
+                         const float* b2, const float* gamma1, const float* beta1, const float* gamma2, const float* beta2,
+                         const float* stats, const float* gout, int64_t ldg, int32_t N, int64_t cap, void* a1, void* dz2,
+                         void* dpre1, void* dP, int64_t lddp, float* part, void* stream) {
+    if (!PQ || !row_ptr || !jc || !plan || !W2p || !W2Tp || !b2 || !gamma1 || !beta1 || !gamma2 || !beta2 || !stats || !gout || !a1 ||
+        !dz2 || !dpre1 || !dP || !part)
+        return bad("gn_edgeconv_norm_bwd", "null argument");
+    hipError_t r = gn::launch_edgeconv_norm_bwd(mode, PQ, H1p, H1, H2, row_ptr, jc, plan, tiles, W2p, W2Tp, b2, gamma1, beta1, gamma2,
+                                                beta2, stats, gout, ldg, N, cap, a1, dz2, dpre1, dP, lddp, part, S(stream));
+    if (r == hipErrorInvalidValue)
+        return bad("gn_edgeconv_norm_bwd", "outside gn_edgeconv_norm_supported, or H1p != ceil32(H1), ldg < H2, lddp < H1p, cap > 64 tiles");
+    return fail(r, "gn_edgeconv_norm_bwd");
+}
 int gn_rev_rows_compact(const int32_t* nbr, const int32_t* ovf_centre, int32_t N, int32_t K, const int32_t* row_ptr,
                         const int32_t* rev_ptr, const int32_t* rev_rows, int32_t* out, void* stream) {
     if (K < 1 || K > 32) return bad("gn_rev_rows_compact", "need 1<=K<=32");

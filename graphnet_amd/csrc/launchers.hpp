@@ -113,6 +113,19 @@ hipError_t launch_edge_bwd_cp(const EdgeGraph& g, const void* PQ, int H1p, int H
 hipError_t launch_dq_gather_cp_saved(int N, int K, int H1p, int H1, int H2, const void* saved, const void* plan, const void* dpre_c,
                                      const void* dpre_ovf, const int* rev_ptr, const int* rev_rows, const int* hubs,
                                      const int* nhubs, void* dQ, long long ldq, hipStream_t st);
+// edgeconv_norm.hip
+bool edgeconv_norm_supported(int mode, int H1, int H2);
+int edgeconv_norm_tiles(int N, int K);
+hipError_t launch_edgeconv_norm_plan(const int* row_ptr, int N, int K, int* plan, hipStream_t st);
+hipError_t launch_edgeconv_norm_fwd(int mode, const float* PQ, int H1p, int H1, int H2, const int* row_ptr, const int* jc,
+                                    const int* plan, int ntiles, const void* W2p, const float* b2, const float* g1, const float* be1,
+                                    const float* g2, const float* be2, float eps, float* out, long long ldo, float* stats,
+                                    hipStream_t st);
+hipError_t launch_edgeconv_norm_bwd(int mode, const float* PQ, int H1p, int H1, int H2, const int* row_ptr, const int* jc,
+                                    const int* plan, int ntiles, const void* W2p, const void* W2Tp, const float* b2, const float* g1,
+                                    const float* be1, const float* g2, const float* be2, const float* stats, const float* gout,
+                                    long long ldg, int N, long long cap, void* a1, void* dz2, void* dpre1, void* dP, long long lddp,
+                                    float* part, hipStream_t st);
 // generic.hip
 hipError_t launch_edge_rows(const EdgeGraph& g, int S, int* ic, int* jc, hipStream_t st);
 hipError_t launch_rows_compact(const EdgeGraph& g, const int* ovf, int* deg, int* tmp, int* row_ptr, int* ic, int* jc, hipStream_t st);

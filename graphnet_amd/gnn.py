@@ -380,6 +380,13 @@ class _DynEdgeFunction(torch.autograd.Function):
         return (None, None) + tuple(grads)
 
 
+def _fused_norm_layer(cfg: dict, mode: int, g, H1: int, H2: int) -> bool:
+    """Whether this convolution layer of :class:`_DynEdgeGenericFunction` runs on the fused LayerNorm + GELU edge kernels:
+    opted in (``cfg["fused_norm"]``), ``Linear, LayerNorm, GELU`` twice, compact rows, widths inside the kernels' envelope."""
+    return bool(cfg.get("fused_norm")) and bool(cfg["norm"]) and cfg["act"] == "gelu" and cfg.get("compact_rows", True) and \
+        g.K <= 32 and ops.edgeconv_norm_supported(mode, H1, H2)
+
+
 class _DynEdgeGenericFunction(torch.autograd.Function):
     """Same contract as :class:`_DynEdgeFunction` for ``activation_layer="gelu"`` and / or
     ``add_norm_layer=True`` (``dynedge.py:160-167,198-231``): the edge MLP runs unfused on edge-row tensors
@@ -420,6 +427,7 @@ class _DynEdgeGenericFunction(torch.autograd.Function):
         x0 = ops.concat_globals(x, gv if G else None, batch, ops.round_up(F0, 32), dtype=adt)
         xs: List[Tuple[Tensor, int]] = [(x0, F0)]
         graphs, saved, knn_coords = [], [], []
+        norm_fused: List[bool] = []                               # per convolution layer: on the fused LayerNorm + GELU kernels
         plan = cfg.get("plan")
         nconv = cfg["nconv"]
         for l, (p1, p2) in enumerate(conv_p):
@@ -460,6 +468,22 @@ class _DynEdgeGenericFunction(torch.autograd.Function):
                 xs.append((out, H2))
                 continue
             PQ = ops.linear_fwd(mode, _ksegs([(xin, Fin)]), ops.pack_weight(Wpq, [Fin], dt, ku), 2 * H1p, bias=bpq)
+            norm_fused.append(not fused and _fused_norm_layer(cfg, mode, g, H1, H2))
+            if norm_fused[-1]:
+                # LayerNorm + GELU edge MLP in one kernel per pass (csrc/edgeconv_norm.hip): no edge-row tensor is kept, the
+                # backward rebuilds the tile from P|Q and 16 bytes of statistics per edge row
+                out, st = ops.edgeconv_norm_fwd(mode, ops.compact_rows(g), PQ, H1p, H1, H2, ops.pack_weight(W2, [H1], dt, 32),
+                                                b2.contiguous(), ln1, ln2)
+                graphs.append(g)
+                saved.append((PQ, st))
+                xs.append((out, H2))
+                if l + 1 < nconv:
+                    cols = _subset_cols(cfg["features_subset"], H2)
+                    if plan is None:
+                        plan = ops.knn_plan(ptr, N)
+                    g = ops.knn_graph(out, cols, batch, ptr, cfg["k"], strict=cfg["strict"], plan=plan)
+                    knn_coords.append(out[:, cols])
+                continue
             # edge rows: the existing edges only (compact: N k + overflow rows; the slot layout has 16 slots for k = 9)
             cr = ops.compact_rows(g) if cfg.get("compact_rows", True) else None
             ic, jc = (cr.ic, cr.jc) if cr is not None else ops.edge_rows(g)
@@ -502,7 +526,7 @@ class _DynEdgeGenericFunction(torch.autograd.Function):
         y_last, P = segs[0]
         ctx.cfg, ctx.xs, ctx.graphs, ctx.saved, ctx.zs, ctx.sts, ctx.params = cfg, xs, graphs, saved, zs, sts, params
         ctx.amin = ctx.amax = None
-        ctx.fused = fused
+        ctx.fused, ctx.norm_fused = fused, norm_fused
         cfg["trace"] = ({"conv_out": [t.float() for t, _ in xs], "graphs": graphs, "post": y_last[:, :P],
                          "knn_coords": knn_coords} if cfg.get("want_trace") else None)
         if cfg["pools"]:
@@ -592,6 +616,16 @@ class _DynEdgeGenericFunction(torch.autograd.Function):
                 ops.edgeconv_bwd(mode, g, PQ, H1p, H2, g_out, mask, ops.pack_weight(W2.t().contiguous(), [H2], dt, 32), dpre,
                                  dPQ[:, :H1p], act=act, H1=H1)
                 ops.edgeconv_dq_gather(mode, g, dpre, H1p, dPQ[:, H1p:])
+            elif ctx.norm_fused[l]:                      # fused LayerNorm + GELU layer: saved (P|Q, statistics)
+                PQ, st = ctx.saved[l]
+                cr = ops.compact_rows(g)
+                dPQ = torch.empty((N, 2 * H1p), dtype=dt, device=dev)
+                a1, dz2, dpre1, dg1, db1n, dg2, db2n = ops.edgeconv_norm_bwd(
+                    mode, cr, PQ, H1p, H1, H2, ops.pack_weight(W2, [H1], dt, 32), ops.pack_weight(W2.t(), [H2], dt, 32),
+                    p2[1].contiguous(), ln1, ln2, st, g_out, dPQ[:, :H1p])
+                dW2, db2 = ops.linear_wgrad(mode, dz2, H2, [(a1, H1p)], with_bias=True)
+                ops.edgeconv_dq_gather(mode, cr.reverse_view(), dpre1, H1p, dPQ[:, H1p:])
+                del PQ, st, a1, dz2, dpre1
             else:
                 cr = ops.compact_rows(g) if cfg.get("compact_rows", True) else None
                 ic, jc = (cr.ic, cr.jc) if cr is not None else ops.edge_rows(g)
@@ -774,11 +808,15 @@ class DynEdge(GNN):
     # ------------------------------------------------------------------ backend control
     def set_backend(self, *, dtype: str = "bf16", knn_mode: str = "compat",
                     graph_columns: Optional[List[int]] = None, overlap: Optional[bool] = None,
-                    step_entry: Optional[bool] = None) -> "DynEdge":
+                    step_entry: Optional[bool] = None, fused_norm_edge: Optional[bool] = None) -> "DynEdge":
         """``dtype``: "bf16" (MFMA bf16 operands, fp32 accumulate) or "fp32" (exact-f32 MFMA,
         parity mode).  ``knn_mode``: "compat" (k+1-with-self then mask, as knn_graph) or
         "strict".  ``graph_columns``: columns for the layer-1 k-NN when the batch carries no
-        ``edge_index`` (KNNGraph default ``[0, 1, 2]``, ``graphs/graphs.py:25``)."""
+        ``edge_index`` (KNNGraph default ``[0, 1, 2]``, ``graphs/graphs.py:25``).  ``fused_norm_edge`` (default off):
+        ``activation_layer="gelu"`` with ``add_norm_layer=True`` runs its convolution layers on the fused LayerNorm + GELU
+        edge kernels (``csrc/edgeconv_norm.hip``) where their widths allow; every other configuration is unaffected."""
+        if fused_norm_edge is not None:
+            self._fused_norm_edge = bool(fused_norm_edge)
         self._compute_mode = {"bf16": ops.MODE_BF16, "fp32": ops.MODE_F32, "f32": ops.MODE_F32}[dtype]
         self._knn_strict = {"compat": False, "strict": True}[knn_mode]
         if graph_columns is not None:
@@ -942,6 +980,7 @@ class DynEdge(GNN):
             # edge-row tensors the backward needs, all layers, fp32: above a quarter of the device's memory they are rebuilt
             # in the backward instead of kept (GN_GENERIC_LEAN=0 / 1 forces either)
             cfg["compact_rows"] = os.environ.get("GN_GENERIC_COMPACT", "1") != "0"
+            cfg["fused_norm"] = bool(getattr(self, "_fused_norm_edge", False))
             rows = int(x.shape[0]) * ((self._nb_neighbours if cfg["compact_rows"] else
                                        int(ops._lib.lib().gn_edge_slots(self._nb_neighbours))) + 1)
             esz = 2 if (cfg["compact_rows"] and self._compute_mode == ops.MODE_BF16) else 4

@@ -378,12 +378,13 @@ class DeepIce(GNN):
         """cls_token should not be subject to weight decay during training."""
         return {"cls_token"}
 
-    def set_backend(self, *, dtype: str = "bf16", knn_mode: str = "compat") -> "DeepIce":
+    def set_backend(self, *, dtype: str = "bf16", knn_mode: str = "compat", fused_norm_edge: Optional[bool] = None) -> "DeepIce":
         """``dtype``: "fp32" (parity mode) or "bf16" (bf16 GEMM operands and plain attention on the matrix core; the residual
-        stream, LayerNorm and the biased attention kernel stay fp32).  Passed on to the embedded ``DynEdge``."""
+        stream, LayerNorm and the biased attention kernel stay fp32).  Passed on to the embedded ``DynEdge``, as is
+        ``fused_norm_edge`` (its fused LayerNorm + GELU edge kernels, default off)."""
         self._compute_mode = {"fp32": ops.MODE_F32, "f32": ops.MODE_F32, "bf16": ops.MODE_BF16}[dtype]
         if self.include_dynedge:
-            self.dyn_edge.set_backend(dtype=dtype, knn_mode=knn_mode)
+            self.dyn_edge.set_backend(dtype=dtype, knn_mode=knn_mode, fused_norm_edge=fused_norm_edge)
         return self
 
     def forward(self, data: Any) -> Tensor:

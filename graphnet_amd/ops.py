@@ -988,6 +988,77 @@ def compact_rows(g: NeighbourTable) -> CompactRows:
     return cached
 
 
+# ------------------------------------------------------------------------------ fused LayerNorm + GELU edge MLP
+def edgeconv_norm_supported(mode: int, H1: int, H2: int) -> bool:
+    """Whether the fused LayerNorm + GELU edge kernels take this layer: the kernels' envelope (``gn_edgeconv_norm_supported``:
+    H1 padded to 32 <= 352, H2 a multiple of 32 <= 256, both modes) and H1 a multiple of 4 - not a limit of the kernels but of
+    ``gn_colsum``, which :func:`edgeconv_norm_bwd` sums the LayerNorm-gradient partials with (as :func:`rownorm_act_bwd` does)."""
+    return H1 % 4 == 0 and bool(_lib.lib().gn_edgeconv_norm_supported(mode, int(H1), int(H2)))
+
+
+def edgeconv_norm_plan(cr: CompactRows) -> Tensor:
+    """Tile plan of :func:`edgeconv_norm_fwd` / ``_bwd`` on the compact rows ``cr``: first centre of every centre-aligned
+    tile of at most 64 rows, ``[tiles + 1]`` int32, built on the device; cached on ``cr``."""
+    plan = getattr(cr, "_norm_plan", None)
+    if plan is None:
+        L = _lib.lib()
+        tiles = int(L.gn_edgeconv_norm_tiles(cr.g.N, cr.g.K))
+        if tiles < 1:
+            raise ValueError("edgeconv_norm_plan: need 1 <= K <= 32")
+        plan = torch.empty(tiles + 1, dtype=torch.int32, device=cr.row_ptr.device)
+        with _timed("generic_edge"):
+            _lib.check(L.gn_edgeconv_norm_plan(_p(cr.row_ptr), cr.g.N, cr.g.K, _p(plan), _st()))
+        cr._norm_plan = plan
+    return plan
+
+
+def edgeconv_norm_fwd(mode: int, cr: CompactRows, PQ: Tensor, H1p: int, H1: int, H2: int, W2p: Tensor, b2: Tensor,
+                      ln1: Tuple[Tensor, Tensor], ln2: Tuple[Tensor, Tensor], eps: float = 1e-5) -> Tuple[Tensor, Tensor]:
+    """``out[i] = sum_j gelu(LN2(gelu(LN1(P[i] + Q[j])) W2^T + b2))`` over the compact rows ``cr`` in one kernel
+    (``gn_edgeconv_norm_fwd``).  ``PQ`` fp32 ``[N, 2 H1p]``, ``W2p = pack_weight(W2, [H1], mode_dtype(mode), 32)``, ``ln*`` =
+    (weight, bias).  Returns (out fp32 ``[N, H2]``, stats fp32 ``[rows, 4]`` = mean1, rstd1, mean2, rstd2 per edge row)."""
+    _need(PQ, torch.float32, "PQ"); _need(W2p, mode_dtype(mode), "W2p"); _need(b2, torch.float32, "b2")
+    for t in (*ln1, *ln2):
+        _need(t, torch.float32, "LayerNorm parameter")
+    plan = edgeconv_norm_plan(cr)
+    N = cr.g.N
+    out = torch.empty((N, H2), dtype=torch.float32, device=PQ.device)
+    stats = torch.empty((cr.rows, 4), dtype=torch.float32, device=PQ.device)
+    with _timed("edgeconv_fwd", f"edgeconv_norm_fwd[{H1p}x{H2}]"):
+        _lib.check(_lib.lib().gn_edgeconv_norm_fwd(mode, _p(PQ), H1p, H1, H2, _p(cr.row_ptr), _p(cr.jc), _p(plan),
+                                                   int(plan.shape[0]) - 1, _p(W2p), _p(b2), _p(ln1[0]), _p(ln1[1]), _p(ln2[0]),
+                                                   _p(ln2[1]), float(eps), _p(out), H2, _p(stats), _st()))
+    return out, stats
+
+
+def edgeconv_norm_bwd(mode: int, cr: CompactRows, PQ: Tensor, H1p: int, H1: int, H2: int, W2p: Tensor, W2Tp: Tensor, b2: Tensor,
+                      ln1: Tuple[Tensor, Tensor], ln2: Tuple[Tensor, Tensor], stats: Tensor, gout: Tensor, dP: Tensor):
+    """Backward of :func:`edgeconv_norm_fwd` (``gn_edgeconv_norm_bwd``).  ``gout`` fp32 ``[N, >= H2]``;
+    ``W2Tp = pack_weight(W2.t(), [H2], mode_dtype(mode), 32)``; ``dP`` ``[N, H1p]`` (a view is fine) in the mode's type is
+    written.  Returns (a1, dz2, dpre1, dgamma1, dbeta1, dgamma2, dbeta2): the three edge-row tensors in the mode's type for
+    :func:`linear_wgrad` (dW2, db2) and :func:`edgeconv_dq_gather` on ``cr.reverse_view()`` (dQ)."""
+    dt = mode_dtype(mode)
+    _need(PQ, torch.float32, "PQ"); _need(W2p, dt, "W2p"); _need(W2Tp, dt, "W2Tp"); _need(stats, torch.float32, "stats")
+    _need(gout, torch.float32, "gout"); _need(dP, dt, "dP")
+    if H1 % 4:
+        raise NotImplementedError("LayerNorm widths must be multiples of 4 on the HIP path (gn_colsum)")
+    plan = edgeconv_norm_plan(cr)
+    tiles = int(plan.shape[0]) - 1
+    dev = PQ.device
+    a1 = torch.empty((cr.rows, H1p), dtype=dt, device=dev)
+    dz2 = torch.empty((cr.rows, H2), dtype=dt, device=dev)
+    dpre1 = torch.empty((cr.rows, H1p), dtype=dt, device=dev)
+    PW = 2 * (H1 + H2)
+    part = torch.empty((tiles, PW), dtype=torch.float32, device=dev)
+    with _timed("edgeconv_bwd", f"edgeconv_norm_bwd[{H1p}x{H2}]"):
+        _lib.check(_lib.lib().gn_edgeconv_norm_bwd(mode, _p(PQ), H1p, H1, H2, _p(cr.row_ptr), _p(cr.jc), _p(plan), tiles, _p(W2p),
+                                                   _p(W2Tp), _p(b2), _p(ln1[0]), _p(ln1[1]), _p(ln2[0]), _p(ln2[1]), _p(stats),
+                                                   _p(gout), _rows(gout, "gout"), cr.g.N, cr.rows, _p(a1), _p(dz2), _p(dpre1),
+                                                   _p(dP), _rows(dP, "dP"), _p(part), _st()))
+    dl1, dl2 = colsum(part[:, :2 * H1], 2 * H1), colsum(part[:, 2 * H1:], 2 * H2)      # (gn_colsum takes <= 1024 columns)
+    return a1, dz2, dpre1, dl1[:H1], dl1[H1:], dl2[:H2], dl2[H2:]
+
+
 def edge_gather_pre(PQ: Tensor, H1p: int, ic: Tensor, jc: Tensor, act: str = "identity", lowp: bool = False) -> Tensor:
     """Edge rows ``act(P[ic] + Q[jc])`` (``act``: "identity" or "leaky_relu"), fp32 or bf16 (``lowp``)."""
     _need(PQ, torch.float32, "PQ")

@@ -411,7 +411,8 @@ int gn_edgeconv_dq_gather(int32_t mode, const void* dpre, int32_t H1p, const int
 /* ---- unfused edge-MLP building blocks: DynEdge(activation_layer="gelu" / add_norm_layer=True) ----------
  * (dynedge.py:160-167,198-231: GELU and LayerNorm after every Linear of the edge and post MLPs.)  The fused
  * kernels above keep one relu bit per activation; GELU / LayerNorm need the pre-activations and a reduction
- * over the whole row, so these variants run on edge-row tensors [N*S + N, .] in HBM, fp32. */
+ * over the whole row, so these variants run on edge-row tensors [N*S + N, .] in HBM, fp32.  (LayerNorm + GELU together also
+ * have a fused family that keeps a tile's whole rows in one workgroup: gn_edgeconv_norm_* below.) */
 /* ic[r], jc[r] = centre / source of edge row r (jc = -1: empty slot), r < N*S + N */
 int gn_edge_rows(const int32_t* nbr, const int32_t* ovf_centre, const int32_t* ovf_src, const int32_t* ovf_cnt,
                  int32_t N, int32_t K, int32_t* ic, int32_t* jc, void* stream);
@@ -454,6 +455,33 @@ int gn_rownorm_act_bwd(const float* g, int64_t ldg, const int32_t* gidx, const f
 int gn_slot_sum(const float* m, int64_t ldm, int32_t C, const int32_t* nbr, const int32_t* ovf_centre,
                 const int32_t* ovf_src, const int32_t* ovf_cnt, int32_t N, int32_t K, float* out, int64_t ldo,
                 void* stream);
+
+/* ---- fused LayerNorm + GELU edge MLP (additions within ABI 7) -------------------------------------------------
+ * out[i] = sum over centre i's edges of gelu(LN2(gelu(LN1(P[i] + Q[j])) . W2^T + b2)) on the compact rows of
+ * gn_rows_compact, without the [E, H] tensors of the building blocks above: a workgroup owns a centre-aligned tile of at
+ * most 64 edge rows with its full width (csrc/edgeconv_norm.hip).  Envelope (gn_edgeconv_norm_supported): mode 0 / 1,
+ * H1 padded to 32 <= 352, H2 a multiple of 32 <= 256; 1 <= K <= 32 (the K gn_rows_compact takes).  H1p = H1 rounded up to 32.
+ * plan: gn_edgeconv_norm_tiles(N, K) + 1 ints (first centre of every tile), filled by gn_edgeconv_norm_plan from row_ptr.
+ * W2p [>= H2 rows][H1p] and W2Tp [>= H1p rows][H2]: the weight and its transpose in the mode's operand type (fp32 / bf16), K
+ * contiguous, zero padded.  PQ, b2, gamma / beta, out, gout, stats [rows, 4] = (mean1, rstd1, mean2, rstd2): fp32.
+ * Backward outputs: a1 [cap, H1p], dz2 [cap, H2], dpre1 [cap, H1p] and dP [N, lddp] in the operand type (cap = N*K + N rows,
+ * zero beyond row_ptr[N]) for gn_linear_wgrad and gn_edgeconv_dq_gather, and part [tiles, 2*(H1 + H2)] fp32 whose column sums
+ * (gn_colsum, which takes multiples of 4 columns up to 1024: the two halves separately, H1 a multiple of 4) are
+ * dgamma1 | dbeta1 | dgamma2 | dbeta2.  No atomics: two runs agree bit for bit.
+ * row_ptr must be gn_rows_compact's (a centre has at most K + 1 rows).  With any other row_ptr a tile of the plan may exceed 64
+ * rows; the kernels then SKIP that tile - out, dP and stats of its centres are left unwritten - and return no error. */
+int32_t gn_edgeconv_norm_supported(int32_t mode, int32_t H1, int32_t H2);
+int32_t gn_edgeconv_norm_tiles(int32_t N, int32_t K);   /* -1: K outside 1..32 */
+int gn_edgeconv_norm_plan(const int32_t* row_ptr, int32_t N, int32_t K, int32_t* plan, void* stream);
+int gn_edgeconv_norm_fwd(int32_t mode, const float* PQ, int32_t H1p, int32_t H1, int32_t H2, const int32_t* row_ptr,
+                         const int32_t* jc, const int32_t* plan, int32_t tiles, const void* W2p, const float* b2,
+                         const float* gamma1, const float* beta1, const float* gamma2, const float* beta2, float eps,
+                         float* out, int64_t ldo, float* stats, void* stream);
+int gn_edgeconv_norm_bwd(int32_t mode, const float* PQ, int32_t H1p, int32_t H1, int32_t H2, const int32_t* row_ptr,
+                         const int32_t* jc, const int32_t* plan, int32_t tiles, const void* W2p, const void* W2Tp,
+                         const float* b2, const float* gamma1, const float* beta1, const float* gamma2, const float* beta2,
+                         const float* stats, const float* gout, int64_t ldg, int32_t N, int64_t cap, void* a1, void* dz2,
+                         void* dpre1, void* dP, int64_t lddp, float* part, void* stream);
 
 /* EdgeConv aggregation over a centre's edge rows (torch_geometric MessagePassing aggr; DynEdgeConv default "max",
  * layers.py:20-50): aggr 0 add, 1 mean, 2 max (first occurrence, centres without edges -> 0).  jc from

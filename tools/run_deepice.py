@@ -15,7 +15,12 @@ _bwd (two lanes per query), everything else as above.
 --shared-bias (head size 32) times the per-head kernels and the ones that form s_ij once for 8 heads (gn_rel_attention_shared_fwd /
 _bwd) on the same batch, and runs the training steps with Attention_rel.shared_bias set.
 
-usage: run_deepice.py [B] [fp32|bf16] [steps] [--icemix] [--head-size {32,64}] [--shared-bias]"""
+--dynedge runs the B+DynEdge shape: DeepIce(include_dynedge=True) with its default embedded DynEdge (nb_inputs 9, 9 neighbours,
+GELU + LayerNorm edge MLPs; three more feature columns derived from the six, a loader-style 6-NN graph over x, y, z, t), with
+--head-size 64 the B+DynEdge_d64 shape.  --fused-norm-edge (implies --dynedge) puts that DynEdge's convolution layers on the fused
+LayerNorm + GELU edge kernels (DeepIce.set_backend(fused_norm_edge=True)); "step_peak_mem_gib" is the peak of the training steps alone.
+
+usage: run_deepice.py [B] [fp32|bf16] [steps] [--icemix] [--head-size {32,64}] [--shared-bias] [--dynedge] [--fused-norm-edge]"""
 import json
 import os
 import sys
@@ -31,7 +36,9 @@ from graphnet_amd.synthetic import synthetic_icecube86_raw            # noqa: E4
 
 ICEMIX = "--icemix" in sys.argv
 SHARED = "--shared-bias" in sys.argv
-argv = [a for a in sys.argv if a not in ("--icemix", "--shared-bias")]
+FUSED_NORM = "--fused-norm-edge" in sys.argv
+DYNEDGE = FUSED_NORM or "--dynedge" in sys.argv
+argv = [a for a in sys.argv if a not in ("--icemix", "--shared-bias", "--dynedge", "--fused-norm-edge")]
 HEAD = 32
 if "--head-size" in argv:
     i = argv.index("--head-size")
@@ -74,6 +81,9 @@ else:
     batch.ptr = ptr_t.to("cuda")
     batch.batch = torch.repeat_interleave(torch.arange(B), torch.from_numpy(n)).to("cuda")
     batch.n_pulses = torch.from_numpy(n).to(torch.int32).to("cuda")
+if DYNEDGE:
+    batch.x = torch.cat([batch.x[:, :6], batch.x[:, 3:6] * 0.5], dim=1).contiguous()      # the embedded DynEdge reads 9 columns
+    batch.edge_index = ops.knn_graph(batch.x, [0, 1, 2, 3], batch.batch.to(torch.int32), batch.ptr.to(torch.int32), 6).edge_index()
 N = int(x.shape[0])
 pairs = int((n.astype(np.int64) ** 2).sum())
 
@@ -119,11 +129,15 @@ pieces["attention_fwd_bf16"] = timed(lambda: ops.attention_fwd(qkv16, H, ptr32, 
 pieces["attention_bwd_bf16"] = timed(lambda: ops.attention_bwd(qkv16, H, ptr32, plan, o16, l16, dout16))
 print(f"B={B} pulses={N} pairs={pairs} heads={H}: " + "  ".join(f"{k} {v:.3f} ms" for k, v in pieces.items()), flush=True)
 del qkv, qp, out, u, dout, du, o32, o16, qkv16, dout16
+pieces_peak = torch.cuda.max_memory_allocated() / 2**30
 
 results = {}
+torch.cuda.synchronize()
+torch.cuda.reset_peak_memory_stats()
 for n_rel in (1, 4):
-    m = g.DeepIce(hidden_dim=HIDDEN, head_size=HEAD, depth=12, depth_rel=4, n_rel=n_rel, seq_length=192).to("cuda")
-    m.set_backend(dtype=dtype)
+    m = g.DeepIce(hidden_dim=HIDDEN, head_size=HEAD, depth=12, depth_rel=4, n_rel=n_rel, seq_length=192,
+                  include_dynedge=DYNEDGE).to("cuda")
+    m.set_backend(dtype=dtype, fused_norm_edge=FUSED_NORM if DYNEDGE else None)
     opt = torch.optim.AdamW(m.parameters(), lr=1e-5, eps=1e-7, weight_decay=0.05, fused=True)
 
     def step():
@@ -150,10 +164,11 @@ for n_rel in (1, 4):
     ops.enable_timers(False)
     results[n_rel] = {"ms_per_step": 1e3 * dt, "events_per_s": B / dt, "loss": float(l),
                       "phase_ms_per_step": {k: ms / 3 for k, (n_, ms) in sorted(summary.items(), key=lambda kv: -kv[1][1])}}
-    print(f"DeepIce B_d{HEAD} n_rel={n_rel} B={B} {dtype}: {1e3 * dt:.2f} ms/step  {B / dt:.0f} events/s  loss {float(l):.4f}", flush=True)
+    print(f"DeepIce B{'+DynEdge' if DYNEDGE else ''}_d{HEAD}{' fused-norm-edge' if FUSED_NORM else ''} n_rel={n_rel} B={B} {dtype}: {1e3 * dt:.2f} ms/step  {B / dt:.0f} events/s  loss {float(l):.4f}", flush=True)
     del m, opt
 
-peak = torch.cuda.max_memory_allocated() / 2**30
+step_peak = torch.cuda.max_memory_allocated() / 2**30
+peak = max(step_peak, pieces_peak)
 print(json.dumps({
     "metric": f"events/sec DeepIce (B_d{HEAD} shape: hidden 768, {H} heads of {HEAD}, 4 + 12 blocks, n_rel 1) fwd+bwd+AdamW, "
               "synthetic IceCube-86",
@@ -164,5 +179,5 @@ print(json.dumps({
     "pieces_ms": pieces,
     "rel_over_plain_fp32": (pieces[REL + "_fwd"] + pieces[REL + "_bwd"]) /
                            (pieces["attention_fwd_fp32"] + pieces["attention_bwd_fp32"]),
-    "peak_mem_gib": peak,
+    "peak_mem_gib": peak, "step_peak_mem_gib": step_peak, "include_dynedge": DYNEDGE, "fused_norm_edge": FUSED_NORM,
     "phase_ms_per_step": {str(k): v["phase_ms_per_step"] for k, v in results.items()}}))
