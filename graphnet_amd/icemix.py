@@ -6,7 +6,8 @@ constructor signatures, defaults and sub-module names, hence the same state-dict
 batch stays ragged (``x``, ``ptr``) and neither tensor exists:
 
 * blocks with the spacetime bias run on ``csrc/attn_rel.hip`` (head width 32; with ``Attention_rel.shared_bias`` on
-  ``csrc/attn_rel_shared.hip``) or ``csrc/attn_rel_wide.hip`` (64).
+  ``csrc/attn_rel_shared.hip``; in bf16 mode with ``Attention_rel.matrix_bias`` on ``csrc/attn_rel_mfma.hip``) or
+  ``csrc/attn_rel_wide.hip`` (64).
   With ``s_ij`` the sinusoidal embedding of the clipped 4-distance and ``R_ij = W s_ij + b`` (``rel_pos.projection``), ``q~ . k + q~ . R_ij = q~ . k + (W^T q~) . s_ij + const`` and
   ``sum_j a_ij (v_j + R_ij) = O_i + W U_i + b`` with ``U_i = sum_j a_ij s_ij``: the kernel takes ``q, k, v`` and ``q' = W^T q~``,
   recomputes ``s_ij`` per pair and returns ``O`` and ``U``; ``W`` and ``b`` stay in two small GEMMs with plain autograd;
@@ -52,14 +53,17 @@ class _RaggedAttentionFunction(torch.autograd.Function):
 class _RelAttentionFunction(torch.autograd.Function):
     """Ragged attention with the spacetime bias recomputed per pair: (qkv ``[N, 3 d]``, qp ``[N, d]``) -> (out, u), both
     ``[N, d]``; ``xt`` and ``freq`` are data.  Head width 64 runs on ``ops.rel_attention_wide_*``, head width 32 on
-    ``ops.rel_attention_*`` or, with ``shared`` (``Attention_rel.shared_bias``), on ``ops.rel_attention_shared_*``."""
+    ``ops.rel_attention_*`` or, with ``shared`` (``Attention_rel.shared_bias``), on ``ops.rel_attention_shared_*``; with
+    ``matrix`` (``Attention_rel.matrix_bias`` in bf16 mode: bf16 ``qkv`` and ``qp``, head width 32) on ``ops.rel_attention_mfma_*``."""
 
     @staticmethod
     def forward(ctx, qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, ptr: Tensor, plan: Tensor,
-                shared: bool = False):  # type: ignore[override]
+                shared: bool = False, matrix: bool = False):  # type: ignore[override]
         qkv, qp = qkv.contiguous(), qp.contiguous()
         dh = int(qp.shape[1]) // n_head
-        if ops.rel_attention_wide_supported(dh):
+        if matrix:
+            fwd, ctx.bwd = ops.rel_attention_mfma_fwd, ops.rel_attention_mfma_bwd
+        elif ops.rel_attention_wide_supported(dh):
             fwd, ctx.bwd = ops.rel_attention_wide_fwd, ops.rel_attention_wide_bwd
         elif shared and ops.rel_attention_shared_supported(dh):
             fwd, ctx.bwd = ops.rel_attention_shared_fwd, ops.rel_attention_shared_bwd
@@ -73,9 +77,9 @@ class _RelAttentionFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout: Tensor, du: Tensor):  # type: ignore[override]
         qkv, qp, xt, freq, ptr, plan, out, u, lse2 = ctx.saved_tensors
-        dqkv, dqp = ctx.bwd(qkv, qp, xt, freq, ctx.n_head, ptr, plan, out, u, lse2, dout.contiguous().to(torch.float32),
-                            du.contiguous().to(torch.float32))
-        return dqkv, dqp, None, None, None, None, None, None
+        dqkv, dqp = ctx.bwd(qkv, qp, xt, freq, ctx.n_head, ptr, plan, out, u, lse2, dout.contiguous().to(qkv.dtype),
+                            du.contiguous().to(qkv.dtype))
+        return dqkv, dqp, None, None, None, None, None, None, None
 
 
 def _rel_width_built(dh: int) -> bool:
@@ -226,9 +230,16 @@ class Attention_rel(Model):
 
     ``shared_bias`` (a class attribute, so that the reference's constructor signature stays): at head width 32 run the
     biased attention on the kernels that form each pair's ``s_ij`` once for 8 heads (``csrc/attn_rel_shared.hip``) instead of
-    once per head; the same results bit for bit.  Off by default."""
+    once per head; the same results bit for bit.  Off by default.
+
+    ``matrix_bias`` (a class attribute likewise): in bf16 mode at head width 32 run the biased attention with bf16 operands on
+    the matrix cores (``csrc/attn_rel_mfma.hip``): ``qkv`` stays bf16, ``qp`` is formed in fp32 and rounded to bf16, ``s_ij`` is
+    rounded once to bf16 inside the kernel; softmax and accumulation stay fp32, and ``out + u Wr^T + br`` is formed in fp32.  The
+    results are those of the fp32 kernels to bf16 accuracy.  No effect in fp32 mode or at head width 64; it takes precedence
+    over ``shared_bias``.  Off by default."""
 
     shared_bias = False
+    matrix_bias = False
 
     def __init__(self, input_dim: int, num_heads: int = 8, qkv_bias: bool = False, qk_scale: Optional[float] = None,
                  attn_drop: float = 0.0, proj_drop: float = 0.0, attn_head_dim: Optional[int] = None):
@@ -273,10 +284,16 @@ class Attention_rel(Model):
             if not _rel_width_built(dh):
                 raise NotImplementedError(f"graphnet_amd.Attention_rel: the biased attention kernels are built for head widths "
                                           f"32 and 64, not {dh}; there is no fallback")
-            qkv = qkv.to(torch.float32)
+            matrix = self.matrix_bias and mode == ops.MODE_BF16 and ops.rel_attention_mfma_supported(dh)
             Wr, br = rel.projection.weight, rel.projection.bias                  # R_ij = Wr s_ij + br
-            qp = torch.matmul(qkv[:, :d].reshape(N, H, dh) * self.scale, Wr).reshape(N, d)      # W^T q~ per head
-            out, u = _RelAttentionFunction.apply(qkv, qp, cfg["xt"], cfg["freq"], H, cfg["ptr"], cfg["plan"], self.shared_bias)
+            if matrix:                                                           # qkv stays bf16; qp in fp32, rounded once
+                qp = torch.matmul(qkv[:, :d].to(torch.float32).reshape(N, H, dh) * self.scale, Wr).reshape(N, d).to(torch.bfloat16)
+                out, u = _RelAttentionFunction.apply(qkv, qp, cfg["xt"], cfg["freq"], H, cfg["ptr"], cfg["plan"], False, True)
+                out, u = out.to(torch.float32), u.to(torch.float32)
+            else:
+                qkv = qkv.to(torch.float32)
+                qp = torch.matmul(qkv[:, :d].reshape(N, H, dh) * self.scale, Wr).reshape(N, d)      # W^T q~ per head
+                out, u = _RelAttentionFunction.apply(qkv, qp, cfg["xt"], cfg["freq"], H, cfg["ptr"], cfg["plan"], self.shared_bias, False)
             att = (out.reshape(N, H, dh) + torch.matmul(u.reshape(N, H, dh), Wr.t()) + br).reshape(N, d)
         return _linear(att, self.proj.weight, self.proj.bias, mode).to(torch.float32)
 

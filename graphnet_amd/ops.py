@@ -1406,21 +1406,32 @@ def rel_attention_shared_supported(dh: int) -> bool:
     return bool(_lib.lib().gn_rel_attention_shared_supported(int(dh)))
 
 
-_REL_FAMILY = {            # kernel family (the stem of its C entries) -> (what the message calls it, the head width it is built for)
-    "rel_attention": ("", 32),
-    "rel_attention_wide": (" (two lanes per query)", 64),
-    "rel_attention_shared": (" (s_ij shared by a group of heads)", 32),
+def rel_attention_mfma_supported(dh: int) -> bool:
+    """Head widths of the biased attention kernels with bf16 operands on the matrix cores
+    (``gn_rel_attention_mfma_supported``): 32."""
+    return bool(_lib.lib().gn_rel_attention_mfma_supported(int(dh)))
+
+
+# kernel family (the stem of its C entries) -> (what the message calls it, the head width it is built for, the type of its rows:
+# qkv, qp, out, u, dout, du and the gradients; xt, freq, lse2 are fp32 in every family)
+_REL_FAMILY = {
+    "rel_attention": ("", 32, torch.float32),
+    "rel_attention_wide": (" (two lanes per query)", 64, torch.float32),
+    "rel_attention_shared": (" (s_ij shared by a group of heads)", 32, torch.float32),
+    "rel_attention_mfma": (" (bf16 operands on the matrix cores)", 32, torch.bfloat16),
 }
 
 
 def _rel_check(qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, family: str) -> Tuple[int, int]:
-    for t, name in ((qkv, "qkv"), (qp, "qp"), (xt, "xt"), (freq, "freq")):
+    what, built, rows = _REL_FAMILY[family]
+    for t, name in ((qkv, "qkv"), (qp, "qp")):
+        _need(t, rows, name)
+    for t, name in ((xt, "xt"), (freq, "freq")):
         _need(t, torch.float32, name)
     N, d = int(qp.shape[0]), int(qp.shape[1])
     if int(qkv.shape[0]) != N or int(qkv.shape[1]) != 3 * d or d % n_head or int(xt.shape[0]) != N or int(xt.shape[1]) < 4:
         raise ValueError("need qkv [N, 3*d], qp [N, d] with d a multiple of the number of heads, xt [N, >= 4]")
     dh = d // n_head
-    what, built = _REL_FAMILY[family]
     if not getattr(_lib.lib(), f"gn_{family}_supported")(dh):
         raise NotImplementedError(f"biased ragged attention{what}: head width {dh} is not built ({built} is); no fallback")
     if int(freq.numel()) != dh // 2 or not freq.is_contiguous():
@@ -1431,8 +1442,8 @@ def _rel_check(qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, f
 def _rel_fwd(qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, ptr: Tensor, plan: Tensor, family: str):
     N, d = _rel_check(qkv, qp, xt, freq, n_head, family)
     B = int(ptr.shape[0]) - 1
-    out = torch.empty((N, d), dtype=torch.float32, device=qkv.device)
-    u = torch.empty((N, d), dtype=torch.float32, device=qkv.device)
+    out = torch.empty((N, d), dtype=qkv.dtype, device=qkv.device)
+    u = torch.empty((N, d), dtype=qkv.dtype, device=qkv.device)
     lse2 = torch.empty((N, n_head), dtype=torch.float32, device=qkv.device)
     name = family + "_fwd"
     with _timed(name):
@@ -1445,11 +1456,12 @@ def _rel_fwd(qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, ptr
 def _rel_bwd(qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, ptr: Tensor, plan: Tensor, out: Tensor, u: Tensor,
              lse2: Tensor, dout: Tensor, du: Tensor, family: str) -> Tuple[Tensor, Tensor]:
     N, d = _rel_check(qkv, qp, xt, freq, n_head, family)
-    for t, name in ((out, "out"), (u, "u"), (dout, "dout"), (du, "du"), (lse2, "lse2")):
-        _need(t, torch.float32, name)
+    for t, name in ((out, "out"), (u, "u"), (dout, "dout"), (du, "du")):
+        _need(t, qkv.dtype, name)
+    _need(lse2, torch.float32, "lse2")
     B = int(ptr.shape[0]) - 1
-    dqkv = torch.empty((N, 3 * d), dtype=torch.float32, device=qkv.device)
-    dqp = torch.empty((N, d), dtype=torch.float32, device=qkv.device)
+    dqkv = torch.empty((N, 3 * d), dtype=qkv.dtype, device=qkv.device)
+    dqp = torch.empty((N, d), dtype=qkv.dtype, device=qkv.device)
     delta = torch.empty((N, n_head), dtype=torch.float32, device=qkv.device)
     name = family + "_bwd"
     with _timed(name):
@@ -1495,6 +1507,20 @@ def rel_attention_shared_bwd(qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, 
                              out: Tensor, u: Tensor, lse2: Tensor, dout: Tensor, du: Tensor) -> Tuple[Tensor, Tensor]:
     """Gradients of :func:`rel_attention_shared_fwd` (``gn_rel_attention_shared_bwd``) -> (dqkv ``[N, 3 d]``, dqp ``[N, d]``)."""
     return _rel_bwd(qkv, qp, xt, freq, n_head, ptr, plan, out, u, lse2, dout, du, "rel_attention_shared")
+
+
+def rel_attention_mfma_fwd(qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, ptr: Tensor, plan: Tensor):
+    """:func:`rel_attention_fwd` (head width 32) with bf16 operands on the matrix cores (``gn_rel_attention_mfma_fwd``): ``qkv``,
+    ``qp`` and the results ``out``, ``u`` are bf16, ``xt``, ``freq`` and ``lse2`` fp32.  ``s_ij`` is formed in fp32 and rounded once to
+    bf16; softmax and accumulation are fp32."""
+    return _rel_fwd(qkv, qp, xt, freq, n_head, ptr, plan, "rel_attention_mfma")
+
+
+def rel_attention_mfma_bwd(qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, ptr: Tensor, plan: Tensor,
+                           out: Tensor, u: Tensor, lse2: Tensor, dout: Tensor, du: Tensor) -> Tuple[Tensor, Tensor]:
+    """Gradients of :func:`rel_attention_mfma_fwd` (``gn_rel_attention_mfma_bwd``; ``dout``, ``du`` bf16) -> (dqkv ``[N, 3 d]``,
+    dqp ``[N, d]``), both bf16."""
+    return _rel_bwd(qkv, qp, xt, freq, n_head, ptr, plan, out, u, lse2, dout, du, "rel_attention_mfma")
 
 
 # ------------------------------------------------------------------------------ TAGConv (ConvNet)

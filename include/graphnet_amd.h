@@ -632,6 +632,30 @@ int gn_rel_attention_shared_bwd(const float* qkv, int64_t ld, const float* qp, i
                                 int64_t lddo, const float* du, int64_t lddu, const float* lse2, float* delta, float* dqkv,
                                 int64_t lddq, float* dqp, int64_t lddqp, void* stream);
 
+/* Head width 32 once more (gn_rel_attention_mfma_supported), with bf16 operands on the matrix cores; a kernel family of its own.
+ * Arguments, validation and the mathematics as gn_rel_attention_fwd / _bwd, any H > 0, but qkv, qp, out, u, dout, du, dqkv and
+ * dqp hold bf16 (pitches in elements, multiples of 8); xt, freq, lse2 and delta[N, H] (scratch: dU . U + dO . O) are fp32.
+ * Rounding points: s_ij is formed in fp32 under the CONTRACT of the pair argument above, unchanged, and then rounded once to
+ * bf16; the probabilities P and dS = P (dA - delta) are rounded to bf16 before their products; every product accumulates in
+ * fp32 (v_mfma_f32_16x16x32_bf16 over the head width, v_mfma_f32_16x16x16_bf16 over a block of 16 rows); the softmax (base 2),
+ * lse2 and delta are fp32; out, u, dqkv, dqp are rounded once as they are stored.  The results are those of the fp32 families
+ * to bf16 accuracy, not bit for bit; an event of one pulse still has out = v bit for bit.
+ * Ownership: one workgroup of 8 waves per (half a 64-row tile of the plan, group g of 16 heads).  The other side of the event
+ * passes in blocks of 16 rows; thread t forms s_ij of one pair of the block.  Products per head (q . k, P . V, dout . v and the
+ * dS products for dq, dk, dv) belong to wave w for heads 16 g + 2 w, 2 w + 1; products per query with the head as the M
+ * dimension (qp . s, du . s, P . s, dS . s) belong to wave w for queries 4 w .. 4 w + 3 of the 32.  Bias scores, P / dS and the
+ * online-softmax rescale factors change layout through LDS once per block.  Heads >= H compute on head H - 1 and store
+ * nothing.  No atomics: two runs agree bit for bit. */
+int gn_rel_attention_mfma_supported(int32_t DH);
+int gn_rel_attention_mfma_fwd(const void* qkv, int64_t ld, const void* qp, int64_t ldqp, const float* xt, int64_t ldxt,
+                              const float* freq, int32_t H, int32_t DH, const int32_t* ptr, const int32_t* tile_ptr, int32_t B,
+                              int32_t N, void* out, int64_t ldo, void* u, int64_t ldu, float* lse2, void* stream);
+int gn_rel_attention_mfma_bwd(const void* qkv, int64_t ld, const void* qp, int64_t ldqp, const float* xt, int64_t ldxt,
+                              const float* freq, int32_t H, int32_t DH, const int32_t* ptr, const int32_t* tile_ptr, int32_t B,
+                              int32_t N, const void* out, int64_t ldo, const void* u, int64_t ldu, const void* dout,
+                              int64_t lddo, const void* du, int64_t lddu, const float* lse2, float* delta, void* dqkv,
+                              int64_t lddq, void* dqp, int64_t lddqp, void* stream);
+
 /* ---- ragged multi-head self attention (DynTrans, models/components/layers.py:166-197) ---- */
 /* Replaces to_dense_batch + torch.nn.TransformerEncoder's attention + x[mask]: every pulse attends to the
  * pulses of its own event (ptr), nothing is padded.  qkv[N, ld] = [Q | K | V], each H*DH wide (the in_proj

@@ -15,12 +15,15 @@ _bwd (two lanes per query), everything else as above.
 --shared-bias (head size 32) times the per-head kernels and the ones that form s_ij once for 8 heads (gn_rel_attention_shared_fwd /
 _bwd) on the same batch, and runs the training steps with Attention_rel.shared_bias set.
 
+--matrix-bias (head size 32, bf16 only) times the per-head kernels, the shared ones and the ones with bf16 operands on the matrix
+cores (gn_rel_attention_mfma_fwd / _bwd) on the same batch, and runs the training steps with Attention_rel.matrix_bias set.
+
 --dynedge runs the B+DynEdge shape: DeepIce(include_dynedge=True) with its default embedded DynEdge (nb_inputs 9, 9 neighbours,
 GELU + LayerNorm edge MLPs; three more feature columns derived from the six, a loader-style 6-NN graph over x, y, z, t), with
 --head-size 64 the B+DynEdge_d64 shape.  --fused-norm-edge (implies --dynedge) puts that DynEdge's convolution layers on the fused
 LayerNorm + GELU edge kernels (DeepIce.set_backend(fused_norm_edge=True)); "step_peak_mem_gib" is the peak of the training steps alone.
 
-usage: run_deepice.py [B] [fp32|bf16] [steps] [--icemix] [--head-size {32,64}] [--shared-bias] [--dynedge] [--fused-norm-edge]"""
+usage: run_deepice.py [B] [fp32|bf16] [steps] [--icemix] [--head-size {32,64}] [--shared-bias] [--matrix-bias] [--dynedge] [--fused-norm-edge]"""
 import json
 import os
 import sys
@@ -36,9 +39,10 @@ from graphnet_amd.synthetic import synthetic_icecube86_raw            # noqa: E4
 
 ICEMIX = "--icemix" in sys.argv
 SHARED = "--shared-bias" in sys.argv
+MATRIX = "--matrix-bias" in sys.argv
 FUSED_NORM = "--fused-norm-edge" in sys.argv
 DYNEDGE = FUSED_NORM or "--dynedge" in sys.argv
-argv = [a for a in sys.argv if a not in ("--icemix", "--shared-bias", "--dynedge", "--fused-norm-edge")]
+argv = [a for a in sys.argv if a not in ("--icemix", "--shared-bias", "--matrix-bias", "--dynedge", "--fused-norm-edge")]
 HEAD = 32
 if "--head-size" in argv:
     i = argv.index("--head-size")
@@ -55,6 +59,9 @@ REL = "rel_attention_wide" if WIDE else "rel_attention"
 B = int(argv[1]) if len(argv) > 1 else 1024
 dtype = argv[2] if len(argv) > 2 else "bf16"
 steps = int(argv[3]) if len(argv) > 3 else 10
+if MATRIX and (WIDE or dtype != "bf16"):
+    sys.exit("--matrix-bias: head size 32 and bf16 only")
+g.Attention_rel.matrix_bias = MATRIX
 MAX_PULSES, HIDDEN = 192, 768
 torch.manual_seed(0)
 
@@ -116,10 +123,18 @@ pieces = {
     REL + "_fwd": timed(lambda: rel_fwd(qkv, qp, xt, freq, H, ptr32, plan)),
     REL + "_bwd": timed(lambda: rel_bwd(qkv, qp, xt, freq, H, ptr32, plan, out, u, lse2, dout, du)),
 }
-if SHARED:
+if SHARED or MATRIX:
     pieces["rel_attention_shared_fwd"] = timed(lambda: ops.rel_attention_shared_fwd(qkv, qp, xt, freq, H, ptr32, plan))
     pieces["rel_attention_shared_bwd"] = timed(lambda: ops.rel_attention_shared_bwd(qkv, qp, xt, freq, H, ptr32, plan, out, u, lse2,
                                                                                    dout, du))
+if MATRIX:
+    bf = torch.bfloat16
+    qkv_b, qp_b, dout_b, du_b = qkv.to(bf), qp.to(bf), dout.to(bf), du.to(bf)
+    out_b, u_b, lse2_b = ops.rel_attention_mfma_fwd(qkv_b, qp_b, xt, freq, H, ptr32, plan)
+    pieces["rel_attention_mfma_fwd"] = timed(lambda: ops.rel_attention_mfma_fwd(qkv_b, qp_b, xt, freq, H, ptr32, plan))
+    pieces["rel_attention_mfma_bwd"] = timed(lambda: ops.rel_attention_mfma_bwd(qkv_b, qp_b, xt, freq, H, ptr32, plan, out_b, u_b,
+                                                                               lse2_b, dout_b, du_b))
+    del qkv_b, qp_b, dout_b, du_b, out_b, u_b, lse2_b
 o32, l32 = ops.attention_fwd(qkv, H, ptr32, plan)
 pieces["attention_fwd_fp32"] = timed(lambda: ops.attention_fwd(qkv, H, ptr32, plan))
 pieces["attention_bwd_fp32"] = timed(lambda: ops.attention_bwd(qkv, H, ptr32, plan, o32, l32, dout))
@@ -172,7 +187,7 @@ peak = max(step_peak, pieces_peak)
 print(json.dumps({
     "metric": f"events/sec DeepIce (B_d{HEAD} shape: hidden 768, {H} heads of {HEAD}, 4 + 12 blocks, n_rel 1) fwd+bwd+AdamW, "
               "synthetic IceCube-86",
-    "value": results[1]["events_per_s"], "unit": "events/s", "n_gpus": 1, "shared_bias": SHARED, "steps": steps, "ms_per_step": results[1]["ms_per_step"],
+    "value": results[1]["events_per_s"], "unit": "events/s", "n_gpus": 1, "shared_bias": SHARED, "matrix_bias": MATRIX, "steps": steps, "ms_per_step": results[1]["ms_per_step"],
     "ms_per_step_n_rel4": results[4]["ms_per_step"], "dtype": dtype, "data": "synthetic",
     "config": {"workload": f"DeepIce(hidden_dim=768, head_size={HEAD}, depth=12, depth_rel=4, seq_length=192) on synthetic IceCube-86 "
                            "events capped at 192 pulses", "events_per_gpu": B, "pulses_per_gpu": N, "pairs_per_gpu": pairs},
