@@ -227,6 +227,16 @@ hipError_t launch_rel_attn_mfma_bwd(const void* qkv, long long ld, const void* q
                                     const void* out, long long ldo, const void* u, long long ldu, const void* dout, long long lddo,
                                     const void* du, long long lddu, const float* lse2, float* delta, void* dqkv, long long lddq,
                                     void* dqp, long long lddqp, hipStream_t st);
+// attn_rel_mfma_wide.hip: the same at head width 64 (a workgroup owns 16 rows, two threads form each pair's s_ij)
+bool rel_attn_mfma_wide_supported(int DH);
+hipError_t launch_rel_attn_mfma_wide_fwd(const void* qkv, long long ld, const void* qp, long long ldqp, const float* xt,
+                                         long long ldxt, const float* freq, int H, int DH, const int* ptr, const int* tile_ptr, int B,
+                                         int N, void* out, long long ldo, void* u, long long ldu, float* lse2, hipStream_t st);
+hipError_t launch_rel_attn_mfma_wide_bwd(const void* qkv, long long ld, const void* qp, long long ldqp, const float* xt,
+                                         long long ldxt, const float* freq, int H, int DH, const int* ptr, const int* tile_ptr, int B,
+                                         int N, const void* out, long long ldo, const void* u, long long ldu, const void* dout,
+                                         long long lddo, const void* du, long long lddu, const float* lse2, float* delta, void* dqkv,
+                                         long long lddq, void* dqp, long long lddqp, hipStream_t st);
 // tagconv.hip: TAGConv(K = 2) - normalised-adjacency propagation, its transpose and the fused layer (fp32 rows, widths % 32, <= 256)
 bool tagconv_supported(int C_in, int C_out);
 hipError_t launch_tag_norm(const int* nbr, const int* ovf, int N, int K, float* dis, hipStream_t st);

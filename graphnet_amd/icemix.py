@@ -7,7 +7,7 @@ batch stays ragged (``x``, ``ptr``) and neither tensor exists:
 
 * blocks with the spacetime bias run on ``csrc/attn_rel.hip`` (head width 32; with ``Attention_rel.shared_bias`` on
   ``csrc/attn_rel_shared.hip``; in bf16 mode with ``Attention_rel.matrix_bias`` on ``csrc/attn_rel_mfma.hip``) or
-  ``csrc/attn_rel_wide.hip`` (64).
+  ``csrc/attn_rel_wide.hip`` (64; in bf16 mode with ``Attention_rel.matrix_bias`` on ``csrc/attn_rel_mfma_wide.hip``).
   With ``s_ij`` the sinusoidal embedding of the clipped 4-distance and ``R_ij = W s_ij + b`` (``rel_pos.projection``), ``q~ . k + q~ . R_ij = q~ . k + (W^T q~) . s_ij + const`` and
   ``sum_j a_ij (v_j + R_ij) = O_i + W U_i + b`` with ``U_i = sum_j a_ij s_ij``: the kernel takes ``q, k, v`` and ``q' = W^T q~``,
   recomputes ``s_ij`` per pair and returns ``O`` and ``U``; ``W`` and ``b`` stay in two small GEMMs with plain autograd;
@@ -54,14 +54,17 @@ class _RelAttentionFunction(torch.autograd.Function):
     """Ragged attention with the spacetime bias recomputed per pair: (qkv ``[N, 3 d]``, qp ``[N, d]``) -> (out, u), both
     ``[N, d]``; ``xt`` and ``freq`` are data.  Head width 64 runs on ``ops.rel_attention_wide_*``, head width 32 on
     ``ops.rel_attention_*`` or, with ``shared`` (``Attention_rel.shared_bias``), on ``ops.rel_attention_shared_*``; with
-    ``matrix`` (``Attention_rel.matrix_bias`` in bf16 mode: bf16 ``qkv`` and ``qp``, head width 32) on ``ops.rel_attention_mfma_*``."""
+    ``matrix`` (``Attention_rel.matrix_bias`` in bf16 mode: bf16 ``qkv`` and ``qp``) on ``ops.rel_attention_mfma_*`` (head width 32)
+    or ``ops.rel_attention_mfma_wide_*`` (64)."""
 
     @staticmethod
     def forward(ctx, qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, ptr: Tensor, plan: Tensor,
                 shared: bool = False, matrix: bool = False):  # type: ignore[override]
         qkv, qp = qkv.contiguous(), qp.contiguous()
         dh = int(qp.shape[1]) // n_head
-        if matrix:
+        if matrix and ops.rel_attention_mfma_wide_supported(dh):
+            fwd, ctx.bwd = ops.rel_attention_mfma_wide_fwd, ops.rel_attention_mfma_wide_bwd
+        elif matrix:
             fwd, ctx.bwd = ops.rel_attention_mfma_fwd, ops.rel_attention_mfma_bwd
         elif ops.rel_attention_wide_supported(dh):
             fwd, ctx.bwd = ops.rel_attention_wide_fwd, ops.rel_attention_wide_bwd
@@ -232,11 +235,11 @@ class Attention_rel(Model):
     biased attention on the kernels that form each pair's ``s_ij`` once for 8 heads (``csrc/attn_rel_shared.hip``) instead of
     once per head; the same results bit for bit.  Off by default.
 
-    ``matrix_bias`` (a class attribute likewise): in bf16 mode at head width 32 run the biased attention with bf16 operands on
-    the matrix cores (``csrc/attn_rel_mfma.hip``): ``qkv`` stays bf16, ``qp`` is formed in fp32 and rounded to bf16, ``s_ij`` is
+    ``matrix_bias`` (a class attribute likewise): in bf16 mode run the biased attention with bf16 operands on the matrix cores
+    (``csrc/attn_rel_mfma.hip`` at head width 32, ``csrc/attn_rel_mfma_wide.hip`` at 64): ``qkv`` stays bf16, ``qp`` is formed in fp32 and rounded to bf16, ``s_ij`` is
     rounded once to bf16 inside the kernel; softmax and accumulation stay fp32, and ``out + u Wr^T + br`` is formed in fp32.  The
-    results are those of the fp32 kernels to bf16 accuracy.  No effect in fp32 mode or at head width 64; it takes precedence
-    over ``shared_bias``.  Off by default."""
+    results are those of the fp32 kernels to bf16 accuracy.  No effect in fp32 mode; it takes precedence over ``shared_bias``.
+    Off by default."""
 
     shared_bias = False
     matrix_bias = False
@@ -284,7 +287,8 @@ class Attention_rel(Model):
             if not _rel_width_built(dh):
                 raise NotImplementedError(f"graphnet_amd.Attention_rel: the biased attention kernels are built for head widths "
                                           f"32 and 64, not {dh}; there is no fallback")
-            matrix = self.matrix_bias and mode == ops.MODE_BF16 and ops.rel_attention_mfma_supported(dh)
+            matrix = self.matrix_bias and mode == ops.MODE_BF16 and (ops.rel_attention_mfma_supported(dh) or
+                                                                     ops.rel_attention_mfma_wide_supported(dh))
             Wr, br = rel.projection.weight, rel.projection.bias                  # R_ij = Wr s_ij + br
             if matrix:                                                           # qkv stays bf16; qp in fp32, rounded once
                 qp = torch.matmul(qkv[:, :d].to(torch.float32).reshape(N, H, dh) * self.scale, Wr).reshape(N, d).to(torch.bfloat16)

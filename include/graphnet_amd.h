@@ -656,6 +656,23 @@ int gn_rel_attention_mfma_bwd(const void* qkv, int64_t ld, const void* qp, int64
                               int64_t lddo, const void* du, int64_t lddu, const float* lse2, float* delta, void* dqkv,
                               int64_t lddq, void* dqp, int64_t lddqp, void* stream);
 
+/* The matrix-core family at head width 64 (gn_rel_attention_mfma_wide_supported; the 32 frequencies of the width): arguments,
+ * validation, rounding points and results as gn_rel_attention_mfma_fwd / _bwd.  A 16x16 score tile takes two
+ * v_mfma_f32_16x16x32_bf16 over the head width, a head's O^T / dq^T / dk^T / dv^T four v_mfma_f32_16x16x16_bf16 column tiles.
+ * Ownership: one workgroup of 8 waves per (QUARTER of a 64-row tile of the plan = 16 rows, group g of 16 heads); the other side
+ * of the event passes in blocks of 16 rows and two threads form each pair's s_ij, 16 of the 32 frequencies each.  Products per
+ * head belong to wave w for heads 16 g + 2 w, 2 w + 1; products per query (the head as the M dimension) to wave w for queries
+ * 2 w, 2 w + 1 of the 16.  Heads >= H compute on head H - 1 and store nothing.  No atomics: two runs agree bit for bit. */
+int gn_rel_attention_mfma_wide_supported(int32_t DH);
+int gn_rel_attention_mfma_wide_fwd(const void* qkv, int64_t ld, const void* qp, int64_t ldqp, const float* xt, int64_t ldxt,
+                                   const float* freq, int32_t H, int32_t DH, const int32_t* ptr, const int32_t* tile_ptr,
+                                   int32_t B, int32_t N, void* out, int64_t ldo, void* u, int64_t ldu, float* lse2, void* stream);
+int gn_rel_attention_mfma_wide_bwd(const void* qkv, int64_t ld, const void* qp, int64_t ldqp, const float* xt, int64_t ldxt,
+                                   const float* freq, int32_t H, int32_t DH, const int32_t* ptr, const int32_t* tile_ptr,
+                                   int32_t B, int32_t N, const void* out, int64_t ldo, const void* u, int64_t ldu,
+                                   const void* dout, int64_t lddo, const void* du, int64_t lddu, const float* lse2, float* delta,
+                                   void* dqkv, int64_t lddq, void* dqp, int64_t lddqp, void* stream);
+
 /* ---- ragged multi-head self attention (DynTrans, models/components/layers.py:166-197) ---- */
 /* Replaces to_dense_batch + torch.nn.TransformerEncoder's attention + x[mask]: every pulse attends to the
  * pulses of its own event (ptr), nothing is padded.  qkv[N, ld] = [Q | K | V], each H*DH wide (the in_proj

@@ -15,8 +15,9 @@ _bwd (two lanes per query), everything else as above.
 --shared-bias (head size 32) times the per-head kernels and the ones that form s_ij once for 8 heads (gn_rel_attention_shared_fwd /
 _bwd) on the same batch, and runs the training steps with Attention_rel.shared_bias set.
 
---matrix-bias (head size 32, bf16 only) times the per-head kernels, the shared ones and the ones with bf16 operands on the matrix
-cores (gn_rel_attention_mfma_fwd / _bwd) on the same batch, and runs the training steps with Attention_rel.matrix_bias set.
+--matrix-bias (bf16 only) times the per-head kernels, the shared ones and the ones with bf16 operands on the matrix cores
+(gn_rel_attention_mfma_fwd / _bwd) on the same batch, and runs the training steps with Attention_rel.matrix_bias set; with
+--head-size 64 it times the matrix-core kernels of that width (gn_rel_attention_mfma_wide_fwd / _bwd) beside the two-lane ones.
 
 --dynedge runs the B+DynEdge shape: DeepIce(include_dynedge=True) with its default embedded DynEdge (nb_inputs 9, 9 neighbours,
 GELU + LayerNorm edge MLPs; three more feature columns derived from the six, a loader-style 6-NN graph over x, y, z, t), with
@@ -59,8 +60,8 @@ REL = "rel_attention_wide" if WIDE else "rel_attention"
 B = int(argv[1]) if len(argv) > 1 else 1024
 dtype = argv[2] if len(argv) > 2 else "bf16"
 steps = int(argv[3]) if len(argv) > 3 else 10
-if MATRIX and (WIDE or dtype != "bf16"):
-    sys.exit("--matrix-bias: head size 32 and bf16 only")
+if MATRIX and dtype != "bf16":
+    sys.exit("--matrix-bias: bf16 only")
 g.Attention_rel.matrix_bias = MATRIX
 MAX_PULSES, HIDDEN = 192, 768
 torch.manual_seed(0)
@@ -123,17 +124,18 @@ pieces = {
     REL + "_fwd": timed(lambda: rel_fwd(qkv, qp, xt, freq, H, ptr32, plan)),
     REL + "_bwd": timed(lambda: rel_bwd(qkv, qp, xt, freq, H, ptr32, plan, out, u, lse2, dout, du)),
 }
-if SHARED or MATRIX:
+if SHARED or (MATRIX and not WIDE):
     pieces["rel_attention_shared_fwd"] = timed(lambda: ops.rel_attention_shared_fwd(qkv, qp, xt, freq, H, ptr32, plan))
     pieces["rel_attention_shared_bwd"] = timed(lambda: ops.rel_attention_shared_bwd(qkv, qp, xt, freq, H, ptr32, plan, out, u, lse2,
                                                                                    dout, du))
 if MATRIX:
     bf = torch.bfloat16
     qkv_b, qp_b, dout_b, du_b = qkv.to(bf), qp.to(bf), dout.to(bf), du.to(bf)
-    out_b, u_b, lse2_b = ops.rel_attention_mfma_fwd(qkv_b, qp_b, xt, freq, H, ptr32, plan)
-    pieces["rel_attention_mfma_fwd"] = timed(lambda: ops.rel_attention_mfma_fwd(qkv_b, qp_b, xt, freq, H, ptr32, plan))
-    pieces["rel_attention_mfma_bwd"] = timed(lambda: ops.rel_attention_mfma_bwd(qkv_b, qp_b, xt, freq, H, ptr32, plan, out_b, u_b,
-                                                                               lse2_b, dout_b, du_b))
+    MFMA = "rel_attention_mfma_wide" if WIDE else "rel_attention_mfma"
+    mfma_fwd, mfma_bwd = getattr(ops, MFMA + "_fwd"), getattr(ops, MFMA + "_bwd")
+    out_b, u_b, lse2_b = mfma_fwd(qkv_b, qp_b, xt, freq, H, ptr32, plan)
+    pieces[MFMA + "_fwd"] = timed(lambda: mfma_fwd(qkv_b, qp_b, xt, freq, H, ptr32, plan))
+    pieces[MFMA + "_bwd"] = timed(lambda: mfma_bwd(qkv_b, qp_b, xt, freq, H, ptr32, plan, out_b, u_b, lse2_b, dout_b, du_b))
     del qkv_b, qp_b, dout_b, du_b, out_b, u_b, lse2_b
 o32, l32 = ops.attention_fwd(qkv, H, ptr32, plan)
 pieces["attention_fwd_fp32"] = timed(lambda: ops.attention_fwd(qkv, H, ptr32, plan))
