@@ -131,6 +131,10 @@ SIGNATURES = {
     "gn_rel_attention_mfma_wide_fwd": (I32, [P, I64, P, I64, P, I64, P, I32, I32, P, P, I32, I32, P, I64, P, I64, P, P]),
     "gn_rel_attention_mfma_wide_bwd": (I32, [P, I64, P, I64, P, I64, P, I32, I32, P, P, I32, I32, P, I64, P, I64, P, I64, P, I64, P,
                                              P, P, I64, P, I64, P]),
+    "gn_rel_attention_wide_shared_supported": (I32, [I32]),
+    "gn_rel_attention_wide_shared_fwd": (I32, [P, I64, P, I64, P, I64, P, I32, I32, P, P, I32, I32, P, I64, P, I64, P, P]),
+    "gn_rel_attention_wide_shared_bwd": (I32, [P, I64, P, I64, P, I64, P, I32, I32, P, P, I32, I32, P, I64, P, I64, P, I64, P, I64, P,
+                                               P, P, I64, P, I64, P]),
     "gn_tagconv_supported": (I32, [I32, I32]),
     "gn_tag_norm": (I32, [P, P, I32, I32, P, P]),
     "gn_tag_propagate": (I32, [P, I64, P, P, P, I32, I32, I32, P, I64, P]),

@@ -237,6 +237,17 @@ hipError_t launch_rel_attn_mfma_wide_bwd(const void* qkv, long long ld, const vo
                                          int N, const void* out, long long ldo, const void* u, long long ldu, const void* dout,
                                          long long lddo, const void* du, long long lddu, const float* lse2, float* delta, void* dqkv,
                                          long long lddq, void* dqp, long long lddqp, hipStream_t st);
+// attn_rel_wide_shared.hip: head width 64 in fp32 with s_ij formed once per pair for a group of heads (arguments as attn_rel_wide.hip)
+bool rel_attn_wide_shared_supported(int DH);
+hipError_t launch_rel_attn_wide_shared_fwd(const float* qkv, long long ld, const float* qp, long long ldqp, const float* xt,
+                                           long long ldxt, const float* freq, int H, int DH, const int* ptr, const int* tile_ptr,
+                                           int B, int N, float* out, long long ldo, float* u, long long ldu, float* lse2,
+                                           hipStream_t st);
+hipError_t launch_rel_attn_wide_shared_bwd(const float* qkv, long long ld, const float* qp, long long ldqp, const float* xt,
+                                           long long ldxt, const float* freq, int H, int DH, const int* ptr, const int* tile_ptr,
+                                           int B, int N, const float* out, long long ldo, const float* u, long long ldu,
+                                           const float* dout, long long lddo, const float* du, long long lddu, const float* lse2,
+                                           float* delta, float* dqkv, long long lddq, float* dqp, long long lddqp, hipStream_t st);
 // tagconv.hip: TAGConv(K = 2) - normalised-adjacency propagation, its transpose and the fused layer (fp32 rows, widths % 32, <= 256)
 bool tagconv_supported(int C_in, int C_out);
 hipError_t launch_tag_norm(const int* nbr, const int* ovf, int N, int K, float* dis, hipStream_t st);

@@ -7,7 +7,8 @@ batch stays ragged (``x``, ``ptr``) and neither tensor exists:
 
 * blocks with the spacetime bias run on ``csrc/attn_rel.hip`` (head width 32; with ``Attention_rel.shared_bias`` on
   ``csrc/attn_rel_shared.hip``; in bf16 mode with ``Attention_rel.matrix_bias`` on ``csrc/attn_rel_mfma.hip``) or
-  ``csrc/attn_rel_wide.hip`` (64; in bf16 mode with ``Attention_rel.matrix_bias`` on ``csrc/attn_rel_mfma_wide.hip``).
+  ``csrc/attn_rel_wide.hip`` (64; with ``Attention_rel.shared_bias`` on ``csrc/attn_rel_wide_shared.hip``; in bf16 mode with
+  ``Attention_rel.matrix_bias`` on ``csrc/attn_rel_mfma_wide.hip``).
   With ``s_ij`` the sinusoidal embedding of the clipped 4-distance and ``R_ij = W s_ij + b`` (``rel_pos.projection``), ``q~ . k + q~ . R_ij = q~ . k + (W^T q~) . s_ij + const`` and
   ``sum_j a_ij (v_j + R_ij) = O_i + W U_i + b`` with ``U_i = sum_j a_ij s_ij``: the kernel takes ``q, k, v`` and ``q' = W^T q~``,
   recomputes ``s_ij`` per pair and returns ``O`` and ``U``; ``W`` and ``b`` stay in two small GEMMs with plain autograd;
@@ -53,7 +54,8 @@ class _RaggedAttentionFunction(torch.autograd.Function):
 class _RelAttentionFunction(torch.autograd.Function):
     """Ragged attention with the spacetime bias recomputed per pair: (qkv ``[N, 3 d]``, qp ``[N, d]``) -> (out, u), both
     ``[N, d]``; ``xt`` and ``freq`` are data.  Head width 64 runs on ``ops.rel_attention_wide_*``, head width 32 on
-    ``ops.rel_attention_*`` or, with ``shared`` (``Attention_rel.shared_bias``), on ``ops.rel_attention_shared_*``; with
+    ``ops.rel_attention_*``; with ``shared`` (``Attention_rel.shared_bias``) they run on ``ops.rel_attention_wide_shared_*`` and
+    ``ops.rel_attention_shared_*``, which give the same bits; with
     ``matrix`` (``Attention_rel.matrix_bias`` in bf16 mode: bf16 ``qkv`` and ``qp``) on ``ops.rel_attention_mfma_*`` (head width 32)
     or ``ops.rel_attention_mfma_wide_*`` (64)."""
 
@@ -66,6 +68,8 @@ class _RelAttentionFunction(torch.autograd.Function):
             fwd, ctx.bwd = ops.rel_attention_mfma_wide_fwd, ops.rel_attention_mfma_wide_bwd
         elif matrix:
             fwd, ctx.bwd = ops.rel_attention_mfma_fwd, ops.rel_attention_mfma_bwd
+        elif shared and ops.rel_attention_wide_shared_supported(dh):
+            fwd, ctx.bwd = ops.rel_attention_wide_shared_fwd, ops.rel_attention_wide_shared_bwd
         elif ops.rel_attention_wide_supported(dh):
             fwd, ctx.bwd = ops.rel_attention_wide_fwd, ops.rel_attention_wide_bwd
         elif shared and ops.rel_attention_shared_supported(dh):
@@ -231,9 +235,10 @@ class Attention_rel(Model):
     the scores and values take, or None for plain attention; ``cfg`` holds ``ptr`` (int32), ``plan``, ``mode`` and, for the
     bias, ``xt`` ``[N, >= 4]`` (x, y, z, time) and ``freq``.
 
-    ``shared_bias`` (a class attribute, so that the reference's constructor signature stays): at head width 32 run the
-    biased attention on the kernels that form each pair's ``s_ij`` once for 8 heads (``csrc/attn_rel_shared.hip``) instead of
-    once per head; the same results bit for bit.  Off by default.
+    ``shared_bias`` (a class attribute, so that the reference's constructor signature stays): run the biased attention on the
+    kernels that form each pair's ``s_ij`` once for a group of heads instead of once per head: 8 heads at head width 32
+    (``csrc/attn_rel_shared.hip``), 4 heads at head width 64 (``csrc/attn_rel_wide_shared.hip``); the same results bit for
+    bit.  Off by default.
 
     ``matrix_bias`` (a class attribute likewise): in bf16 mode run the biased attention with bf16 operands on the matrix cores
     (``csrc/attn_rel_mfma.hip`` at head width 32, ``csrc/attn_rel_mfma_wide.hip`` at 64): ``qkv`` stays bf16, ``qp`` is formed in fp32 and rounded to bf16, ``s_ij`` is

@@ -1418,6 +1418,12 @@ def rel_attention_mfma_wide_supported(dh: int) -> bool:
     return bool(_lib.lib().gn_rel_attention_mfma_wide_supported(int(dh)))
 
 
+def rel_attention_wide_shared_supported(dh: int) -> bool:
+    """Head widths of the two-lanes-per-query biased attention kernels that form ``s_ij`` once per pair for a group of heads
+    (``gn_rel_attention_wide_shared_supported``): 64."""
+    return bool(_lib.lib().gn_rel_attention_wide_shared_supported(int(dh)))
+
+
 # kernel family (the stem of its C entries) -> (what the message calls it, the head width it is built for, the type of its rows:
 # qkv, qp, out, u, dout, du and the gradients; xt, freq, lse2 are fp32 in every family)
 _REL_FAMILY = {
@@ -1426,6 +1432,7 @@ _REL_FAMILY = {
     "rel_attention_shared": (" (s_ij shared by a group of heads)", 32, torch.float32),
     "rel_attention_mfma": (" (bf16 operands on the matrix cores)", 32, torch.bfloat16),
     "rel_attention_mfma_wide": (" (bf16 operands on the matrix cores, 16 rows per workgroup)", 64, torch.bfloat16),
+    "rel_attention_wide_shared": (" (two lanes per query, s_ij shared by a group of heads)", 64, torch.float32),
 }
 
 
@@ -1541,6 +1548,19 @@ def rel_attention_mfma_wide_bwd(qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tenso
     """Gradients of :func:`rel_attention_mfma_wide_fwd` (``gn_rel_attention_mfma_wide_bwd``; ``dout``, ``du`` bf16) -> (dqkv
     ``[N, 3 d]``, dqp ``[N, d]``), both bf16."""
     return _rel_bwd(qkv, qp, xt, freq, n_head, ptr, plan, out, u, lse2, dout, du, "rel_attention_mfma_wide")
+
+
+def rel_attention_wide_shared_fwd(qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, ptr: Tensor, plan: Tensor):
+    """:func:`rel_attention_wide_fwd` (head width 64, the same bits) on ``gn_rel_attention_wide_shared_fwd``: one workgroup serves
+    4 heads and evaluates each pair's ``s_ij`` once for all of them."""
+    return _rel_fwd(qkv, qp, xt, freq, n_head, ptr, plan, "rel_attention_wide_shared")
+
+
+def rel_attention_wide_shared_bwd(qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, ptr: Tensor, plan: Tensor,
+                                  out: Tensor, u: Tensor, lse2: Tensor, dout: Tensor, du: Tensor) -> Tuple[Tensor, Tensor]:
+    """Gradients of :func:`rel_attention_wide_shared_fwd` (``gn_rel_attention_wide_shared_bwd``) -> (dqkv ``[N, 3 d]``,
+    dqp ``[N, d]``)."""
+    return _rel_bwd(qkv, qp, xt, freq, n_head, ptr, plan, out, u, lse2, dout, du, "rel_attention_wide_shared")
 
 
 # ------------------------------------------------------------------------------ TAGConv (ConvNet)

@@ -673,6 +673,27 @@ int gn_rel_attention_mfma_wide_bwd(const void* qkv, int64_t ld, const void* qp, 
                                    const void* dout, int64_t lddo, const void* du, int64_t lddu, const float* lse2, float* delta,
                                    void* dqkv, int64_t lddq, void* dqp, int64_t lddqp, void* stream);
 
+/* Head width 64 in fp32 again (gn_rel_attention_wide_shared_supported), with s_ij formed once per pair for a group of 4 heads
+ * instead of once per head; a kernel family of its own: arguments, validation, pair-argument contract and results as
+ * gn_rel_attention_wide_fwd / _bwd, any H > 0; gn_rel_attention_shared_supported(64) stays 0.
+ * Ownership: one workgroup of 8 waves per (64-row tile of the plan, group g of 4 heads); the wave pair (2 p, 2 p + 1) serves
+ * head 4 g + p with the rows, halves and columns of a gn_rel_attention_wide_fwd workgroup (a pair whose head is >= H only
+ * helps to form s_ij).  The other side of the event passes through LDS 4 rows at a time; wave pair p forms s_ij of the block's
+ * row p for the 128 (row, half) lanes of the tile, every wave reads all 4 rows back.  Per head the summation order is that of
+ * gn_rel_attention_wide_fwd / _bwd (per half the bias terms first, then the row-side terms, half0 + half1, online softmax key
+ * by key, delta summed as dA): the results are the same bits, an event of one pulse has dq = dk = dqp = 0 exactly and
+ * out = v bit for bit.  No atomics. */
+int gn_rel_attention_wide_shared_supported(int32_t DH);
+int gn_rel_attention_wide_shared_fwd(const float* qkv, int64_t ld, const float* qp, int64_t ldqp, const float* xt, int64_t ldxt,
+                                     const float* freq, int32_t H, int32_t DH, const int32_t* ptr, const int32_t* tile_ptr,
+                                     int32_t B, int32_t N, float* out, int64_t ldo, float* u, int64_t ldu, float* lse2,
+                                     void* stream);
+int gn_rel_attention_wide_shared_bwd(const float* qkv, int64_t ld, const float* qp, int64_t ldqp, const float* xt, int64_t ldxt,
+                                     const float* freq, int32_t H, int32_t DH, const int32_t* ptr, const int32_t* tile_ptr,
+                                     int32_t B, int32_t N, const float* out, int64_t ldo, const float* u, int64_t ldu,
+                                     const float* dout, int64_t lddo, const float* du, int64_t lddu, const float* lse2,
+                                     float* delta, float* dqkv, int64_t lddq, float* dqp, int64_t lddqp, void* stream);
+
 /* ---- ragged multi-head self attention (DynTrans, models/components/layers.py:166-197) ---- */
 /* Replaces to_dense_batch + torch.nn.TransformerEncoder's attention + x[mask]: every pulse attends to the
  * pulses of its own event (ptr), nothing is padded.  qkv[N, ld] = [Q | K | V], each H*DH wide (the in_proj

@@ -12,8 +12,9 @@ first 192; the default workload is the host loop, so that its numbers stay compa
 --head-size 64 runs the B_d64 shape instead (hidden 768, 12 heads of 64): the biased blocks on gn_rel_attention_wide_fwd /
 _bwd (two lanes per query), everything else as above.
 
---shared-bias (head size 32) times the per-head kernels and the ones that form s_ij once for 8 heads (gn_rel_attention_shared_fwd /
-_bwd) on the same batch, and runs the training steps with Attention_rel.shared_bias set.
+--shared-bias times the per-head kernels and the ones that form s_ij once for a group of heads on the same batch (head size 32:
+8 heads, gn_rel_attention_shared_fwd / _bwd; --head-size 64: 4 heads, gn_rel_attention_wide_shared_fwd / _bwd), and runs the
+training steps with Attention_rel.shared_bias set.
 
 --matrix-bias (bf16 only) times the per-head kernels, the shared ones and the ones with bf16 operands on the matrix cores
 (gn_rel_attention_mfma_fwd / _bwd) on the same batch, and runs the training steps with Attention_rel.matrix_bias set; with
@@ -52,11 +53,10 @@ if "--head-size" in argv:
 if HEAD not in (32, 64):
     sys.exit("--head-size: 32 or 64")
 WIDE = HEAD == 64
-if SHARED and WIDE:
-    sys.exit("--shared-bias: head size 32 only")
 g.Attention_rel.shared_bias = SHARED
 rel_fwd, rel_bwd = (ops.rel_attention_wide_fwd, ops.rel_attention_wide_bwd) if WIDE else (ops.rel_attention_fwd, ops.rel_attention_bwd)
 REL = "rel_attention_wide" if WIDE else "rel_attention"
+REL_SHARED = "rel_attention_wide_shared" if WIDE else "rel_attention_shared"
 B = int(argv[1]) if len(argv) > 1 else 1024
 dtype = argv[2] if len(argv) > 2 else "bf16"
 steps = int(argv[3]) if len(argv) > 3 else 10
@@ -125,9 +125,9 @@ pieces = {
     REL + "_bwd": timed(lambda: rel_bwd(qkv, qp, xt, freq, H, ptr32, plan, out, u, lse2, dout, du)),
 }
 if SHARED or (MATRIX and not WIDE):
-    pieces["rel_attention_shared_fwd"] = timed(lambda: ops.rel_attention_shared_fwd(qkv, qp, xt, freq, H, ptr32, plan))
-    pieces["rel_attention_shared_bwd"] = timed(lambda: ops.rel_attention_shared_bwd(qkv, qp, xt, freq, H, ptr32, plan, out, u, lse2,
-                                                                                   dout, du))
+    shared_fwd, shared_bwd = getattr(ops, REL_SHARED + "_fwd"), getattr(ops, REL_SHARED + "_bwd")
+    pieces[REL_SHARED + "_fwd"] = timed(lambda: shared_fwd(qkv, qp, xt, freq, H, ptr32, plan))
+    pieces[REL_SHARED + "_bwd"] = timed(lambda: shared_bwd(qkv, qp, xt, freq, H, ptr32, plan, out, u, lse2, dout, du))
 if MATRIX:
     bf = torch.bfloat16
     qkv_b, qp_b, dout_b, du_b = qkv.to(bf), qp.to(bf), dout.to(bf), du.to(bf)
