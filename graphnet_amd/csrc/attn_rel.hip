@@ -24,22 +24,6 @@
 
 namespace gn {
 
-// frequencies in revolutions per unit, hi + lo, wave-uniform (lane k forms entry k in double, then it is broadcast)
-template <int HF>
-__device__ __forceinline__ void rel_freq_table(const float* __restrict__ freq, int lane, float (&ghi)[HF], float (&glo)[HF]) {
-    float hi_l = 0.0f, lo_l = 0.0f;
-    if (lane < HF) {
-        const double g = (double)freq[lane] * 0.15915494309189534561;
-        hi_l = (float)g;
-        lo_l = (float)(g - (double)hi_l);
-    }
-#pragma unroll
-    for (int k = 0; k < HF; ++k) {
-        ghi[k] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, hi_l), k));
-        glo[k] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, lo_l), k));
-    }
-}
-
 #define REL_TILE_PROLOGUE(ROW0, ROWI) REL_TILE_PROLOGUE_AT(ROW0, ROWI, lane)
 
 template <int DH>
@@ -54,7 +38,7 @@ __global__ __launch_bounds__(64) void rel_attn_fwd_kernel(
     __shared__ float4 Xs[REL_TILE];
     REL_TILE_PROLOGUE(q0, qi)
     float ghi[HF], glo[HF];
-    rel_freq_table<HF>(freq, lane, ghi, glo);
+    rel_freq_table<HF>(freq, 0, lane, ghi, glo);
     const float4 xi = rel_load_xt(xt, ldxt, myrow);
     float q[DH], qq[DH], o[DH], uu[DH];
 #pragma unroll
@@ -139,7 +123,7 @@ __global__ __launch_bounds__(64) void rel_attn_bwd_dq_kernel(
     __shared__ float4 Xs[REL_TILE];
     REL_TILE_PROLOGUE(q0, qi)
     float ghi[HF], glo[HF];
-    rel_freq_table<HF>(freq, lane, ghi, glo);
+    rel_freq_table<HF>(freq, 0, lane, ghi, glo);
     const float4 xi = rel_load_xt(xt, ldxt, myrow);
     const float scale2 = scale * REL_LOG2E;
     float q[DH], qq[DH], go[DH], gu[DH], dq[DH], dqq[DH];
@@ -246,7 +230,7 @@ __global__ __launch_bounds__(64) void rel_attn_bwd_dkv_kernel(
     __shared__ float4 Xs[QT];
     REL_TILE_PROLOGUE(k0, kj)
     float ghi[HF], glo[HF];
-    rel_freq_table<HF>(freq, lane, ghi, glo);
+    rel_freq_table<HF>(freq, 0, lane, ghi, glo);
     const float4 xj = rel_load_xt(xt, ldxt, myrow);
     const float scale2 = scale * REL_LOG2E;
     float k[DH], v[DH], dk[DH], dv[DH];
@@ -324,38 +308,35 @@ __global__ __launch_bounds__(64) void rel_attn_bwd_dkv_kernel(
 
 bool rel_attn_supported(int DH) { return DH == 32; }
 
-hipError_t launch_rel_attn_fwd(const float* qkv, long long ld, const float* qp, long long ldqp, const float* xt, long long ldxt,
+hipError_t launch_rel_attn_fwd(const void* qkv, long long ld, const void* qp, long long ldqp, const float* xt, long long ldxt,
                                const float* freq, int H, int DH, const int* ptr, const int* tile_ptr, int B, int N,
-                               float* out, long long ldo, float* u, long long ldu, float* lse2, hipStream_t st) {
-    if (!rel_attn_supported(DH) || ld % 4 || ldqp % 4 || ldo % 4 || ldu % 4 || ldxt < 4 || ld < 3ll * H * DH ||
-        ldqp < (long long)H * DH || ldo < (long long)H * DH || ldu < (long long)H * DH)
-        return hipErrorInvalidValue;
+                               void* out, long long ldo, void* u, long long ldu, float* lse2, hipStream_t st) {
+    if (!rel_attn_supported(DH) || !rel_args_ok(false, 4, H, DH, ld, ldqp, ldxt, ldo, ldu)) return hipErrorInvalidValue;
     if (N == 0 || B == 0) return hipSuccess;
     const dim3 grid((unsigned)(N / REL_TILE + B), (unsigned)H), block(REL_TILE);
-    const float scale2 = REL_LOG2E / sqrtf((float)DH);
-    hipLaunchKernelGGL((rel_attn_fwd_kernel<32>), grid, block, 0, st, qkv, ld, qp, ldqp, xt, ldxt, freq, H, ptr, tile_ptr, B,
-                       scale2, out, ldo, u, ldu, lse2);
+    hipLaunchKernelGGL((rel_attn_fwd_kernel<32>), grid, block, 0, st, (const float*)qkv, ld, (const float*)qp, ldqp, xt, ldxt, freq,
+                       H, ptr, tile_ptr, B, rel_scale2(DH), (float*)out, ldo, (float*)u, ldu, lse2);
     return hipGetLastError();
 }
 
-hipError_t launch_rel_attn_bwd(const float* qkv, long long ld, const float* qp, long long ldqp, const float* xt, long long ldxt,
+hipError_t launch_rel_attn_bwd(const void* qkv, long long ld, const void* qp, long long ldqp, const float* xt, long long ldxt,
                                const float* freq, int H, int DH, const int* ptr, const int* tile_ptr, int B, int N,
-                               const float* out, long long ldo, const float* u, long long ldu, const float* dout,
-                               long long lddo, const float* du, long long lddu, const float* lse2, float* delta,
-                               float* dqkv, long long lddq, float* dqp, long long lddqp, hipStream_t st) {
-    const long long d = (long long)H * DH;
-    if (!rel_attn_supported(DH) || ld % 4 || ldqp % 4 || ldo % 4 || ldu % 4 || lddo % 4 || lddu % 4 || lddq % 4 || lddqp % 4 ||
-        ldxt < 4 || ld < 3 * d || lddq < 3 * d || ldqp < d || ldo < d || ldu < d || lddo < d || lddu < d || lddqp < d)
+                               const void* out, long long ldo, const void* u, long long ldu, const void* dout,
+                               long long lddo, const void* du, long long lddu, const float* lse2, float* delta,
+                               void* dqkv, long long lddq, void* dqp, long long lddqp, hipStream_t st) {
+    if (!rel_attn_supported(DH) || !rel_args_ok(true, 4, H, DH, ld, ldqp, ldxt, ldo, ldu, lddo, lddu, lddq, lddqp))
         return hipErrorInvalidValue;
     if (N == 0 || B == 0) return hipSuccess;
     const dim3 grid((unsigned)(N / REL_TILE + B), (unsigned)H), block(REL_TILE);
-    const float scale = 1.0f / sqrtf((float)DH);
+    const float scale = rel_scale(DH);
     // (the templates are written for any even DH; at DH = 64 the dQ pass holds six row vectors and s_ij, 448 registers,
     //  and spills - only 32 is instantiated, see rel_attn_supported; head width 64 runs on attn_rel_wide.hip)
-    hipLaunchKernelGGL((rel_attn_bwd_dq_kernel<32>), grid, block, 0, st, qkv, ld, qp, ldqp, xt, ldxt, freq, H, ptr, tile_ptr,
-                       B, scale, out, ldo, u, ldu, dout, lddo, du, lddu, lse2, delta, dqkv, lddq, dqp, lddqp);
-    hipLaunchKernelGGL((rel_attn_bwd_dkv_kernel<32, REL_TILE>), grid, block, 0, st, qkv, ld, qp, ldqp, xt, ldxt, freq, H, ptr,
-                       tile_ptr, B, scale, dout, lddo, du, lddu, lse2, delta, dqkv, lddq);
+    hipLaunchKernelGGL((rel_attn_bwd_dq_kernel<32>), grid, block, 0, st, (const float*)qkv, ld, (const float*)qp, ldqp, xt, ldxt,
+                       freq, H, ptr, tile_ptr, B, scale, (const float*)out, ldo, (const float*)u, ldu, (const float*)dout, lddo,
+                       (const float*)du, lddu, lse2, delta, (float*)dqkv, lddq, (float*)dqp, lddqp);
+    hipLaunchKernelGGL((rel_attn_bwd_dkv_kernel<32, REL_TILE>), grid, block, 0, st, (const float*)qkv, ld, (const float*)qp, ldqp,
+                       xt, ldxt, freq, H, ptr, tile_ptr, B, scale, (const float*)dout, lddo, (const float*)du, lddu, lse2, delta,
+                       (float*)dqkv, lddq);
     return hipGetLastError();
 }
 

@@ -1,8 +1,10 @@
-// graphnet_amd/csrc/attn_rel.hpp — what the two kernel families of the spacetime-bias attention share (attn_rel.hip: head
-// width 32, one lane per query; attn_rel_wide.hip: head width 64, two lanes per query): the tile prologue over the plan of
-// gn_attention_plan, the LDS staging, and the pair argument with its sine / cosine (a CONTRACT, include/graphnet_amd.h).
+// graphnet_amd/csrc/attn_rel.hpp — what the six kernel families of the spacetime-bias attention share (attn_rel*.hip): the
+// pair argument with its sine / cosine and the hi / lo frequency table (a CONTRACT, include/graphnet_amd.h), the event lookup
+// over the plan of gn_attention_plan, LDS staging, the row and s_ij helpers of the fp32 families, and the host-side argument
+// check, LDS opt-in and score scales of every launcher.  The matrix-core helpers are in attn_rel_mfma.hpp.
 #pragma once
 #include "common.hpp"
+#include <cmath>
 
 namespace gn {
 
@@ -83,17 +85,118 @@ __device__ __forceinline__ void rel_sincos(float a, float ghi, float glo, float&
     cs = __builtin_bit_cast(float, uc);
 }
 
-// Tile -> event and rows.  `lane` is the thread of the workgroup; ROWOFF (an expression of `lane`) is its row in the tile.
-#define REL_TILE_PROLOGUE_AT(ROW0, ROWI, ROWOFF)                                                                \
-    const int tile = blockIdx.x, head = blockIdx.y, lane = threadIdx.x;                                         \
+// frequencies [HF fb, HF fb + HF), block fb of the table, in revolutions per unit, hi + lo, wave-uniform (lane k forms entry k in
+// double, then it is broadcast)
+template <int HF>
+__device__ __forceinline__ void rel_freq_table(const float* __restrict__ freq, int fb, int lane, float (&ghi)[HF], float (&glo)[HF]) {
+    float hi_l = 0.0f, lo_l = 0.0f;
+    if (lane < HF) {
+        const double g = (double)freq[HF * fb + lane] * 0.15915494309189534561;
+        hi_l = (float)g;
+        lo_l = (float)(g - (double)hi_l);
+    }
+#pragma unroll
+    for (int k = 0; k < HF; ++k) {
+        ghi[k] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, hi_l), k));
+        glo[k] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, lo_l), k));
+    }
+}
+
+// two lanes per row (attn_rel_wide.hip, attn_rel_wide_shared.hip): x of this lane + x of its partner lane l ^ 32, as
+// half0 + half1 on both
+__device__ __forceinline__ float rel_pair_sum(float x) {
+    const unsigned b = __builtin_bit_cast(unsigned, x);
+    const auto r = __builtin_amdgcn_permlane32_swap(b, b, false, false);     // {x of lane l & 31, x of lane 32 + (l & 31)}
+    return __builtin_bit_cast(float, (unsigned)r[0]) + __builtin_bit_cast(float, (unsigned)r[1]);
+}
+
+// W contiguous floats at p (16-byte aligned), times mul
+template <int W>
+__device__ __forceinline__ void rel_load_row(float (&dst)[W], const float* __restrict__ p, float mul) {
+#pragma unroll
+    for (int d4 = 0; d4 < W / 4; ++d4) {
+        const float4 v = *reinterpret_cast<const float4*>(p + 4 * d4);
+        dst[4 * d4] = v.x * mul; dst[4 * d4 + 1] = v.y * mul; dst[4 * d4 + 2] = v.z * mul; dst[4 * d4 + 3] = v.w * mul;
+    }
+}
+
+template <int W>
+__device__ __forceinline__ void rel_store_row(float* __restrict__ p, const float (&src)[W], float mul) {
+#pragma unroll
+    for (int d4 = 0; d4 < W / 4; ++d4)
+        *reinterpret_cast<float4*>(p + 4 * d4) =
+            make_float4(src[4 * d4] * mul, src[4 * d4 + 1] * mul, src[4 * d4 + 2] * mul, src[4 * d4 + 3] * mul);
+}
+
+// the embedding half of a lane at head width 64, at p = row + head * 64 + 16 h: dst[k] = sine column p[k],
+// dst[16 + k] = cosine column p[32 + k]
+__device__ __forceinline__ void rel_load_emb(float (&dst)[32], const float* __restrict__ p, float mul) {
+#pragma unroll
+    for (int part = 0; part < 2; ++part)
+#pragma unroll
+        for (int d4 = 0; d4 < 4; ++d4) {
+            const float4 v = *reinterpret_cast<const float4*>(p + 32 * part + 4 * d4);
+            float* d = dst + 16 * part + 4 * d4;
+            d[0] = v.x * mul; d[1] = v.y * mul; d[2] = v.z * mul; d[3] = v.w * mul;
+        }
+}
+
+__device__ __forceinline__ void rel_store_emb(float* __restrict__ p, const float (&src)[32], float mul) {
+#pragma unroll
+    for (int part = 0; part < 2; ++part)
+#pragma unroll
+        for (int d4 = 0; d4 < 4; ++d4) {
+            const float* s = src + 16 * part + 4 * d4;
+            *reinterpret_cast<float4*>(p + 32 * part + 4 * d4) = make_float4(s[0] * mul, s[1] * mul, s[2] * mul, s[3] * mul);
+        }
+}
+
+// the shared-embedding families: s_ij of a block row is [chunk j < W / 4][unit < UNITS][4 floats]; this unit's W values
+template <int W, int UNITS>
+__device__ __forceinline__ void rel_read(float (&sc)[W], const float* __restrict__ srow, int unit) {
+#pragma unroll
+    for (int j = 0; j < W / 4; ++j) {
+        const float4 v = *reinterpret_cast<const float4*>(srow + (j * UNITS + unit) * 4);
+        sc[4 * j] = v.x; sc[4 * j + 1] = v.y; sc[4 * j + 2] = v.z; sc[4 * j + 3] = v.w;
+    }
+}
+
+// Tile `tile` of the plan of gn_attention_plan -> its event's rows [kbeg, kend) and TILE0, the first row of the tile.  The one
+// `return` (a tile past the plan's last) depends on `tile` alone: a workgroup leaves as a whole before its first barrier.
+#define REL_EVENT_PROLOGUE(TILE0)                                                                               \
     if (tile >= tile_ptr[B]) return;                                                                            \
     const int es = rel_event_of_tile(tile_ptr, B, tile);                                                        \
     const int e = tile_ptr[B + 1 + es];                                                                         \
     const int kbeg = ptr[e], kend = ptr[e + 1];                                                                 \
-    const int ROW0 = kbeg + (tile - tile_ptr[es]) * REL_TILE;                                                   \
+    const int TILE0 = kbeg + (tile - tile_ptr[es]) * REL_TILE;
+
+// Tile -> event and rows.  `lane` is the thread of the workgroup; ROWOFF (an expression of `lane`) is its row in the tile.
+#define REL_TILE_PROLOGUE_AT(ROW0, ROWI, ROWOFF)                                                                \
+    const int tile = blockIdx.x, head = blockIdx.y, lane = threadIdx.x;                                         \
+    REL_EVENT_PROLOGUE(ROW0)                                                                                    \
     const int E = H * DH;                                                                                       \
     const int ROWI = ROW0 + (ROWOFF);                                                                           \
     const bool valid = ROWI < kend;                                                                             \
     const int myrow = valid ? ROWI : kend - 1;
+
+// ---- host side of every launcher ----
+// Row pitches (in elements) of a forward (`bwd` false: lddo .. lddqp are not looked at) or a backward: multiples of `vec`
+// elements = 16 bytes (4 fp32, 8 bf16) and at least the row width; xt holds x, y, z, time.
+inline bool rel_args_ok(bool bwd, int vec, int H, int DH, long long ld, long long ldqp, long long ldxt, long long ldo,
+                        long long ldu, long long lddo = 0, long long lddu = 0, long long lddq = 0, long long lddqp = 0) {
+    const long long d = (long long)H * DH;
+    if (ld % vec || ldqp % vec || ldo % vec || ldu % vec || ldxt < 4 || ld < 3 * d || ldqp < d || ldo < d || ldu < d) return false;
+    return !bwd || !(lddo % vec || lddu % vec || lddq % vec || lddqp % vec || lddq < 3 * d || lddo < d || lddu < d || lddqp < d);
+}
+
+// more than 64 KB of dynamic LDS has to be asked for once per kernel
+template <typename K>
+inline hipError_t rel_allow_lds(K kernel, int bytes) {
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+}
+
+// what the scores are scaled by: 1 / sqrt(dh), and the same in the exp2 domain
+inline float rel_scale(int DH) { return 1.0f / sqrtf((float)DH); }
+inline float rel_scale2(int DH) { return REL_LOG2E / sqrtf((float)DH); }
 
 }  // namespace gn

@@ -25,7 +25,7 @@
 // head, the row or the lane.  Heads past H - 1 compute on head H - 1 and rows past the event on its last row (every load is
 // clamped), and store nothing.  The two `return`s depend on blockIdx.x and the event alone: a workgroup leaves as a whole
 // before its first barrier.  No atomics; no packed fp32 operations.
-#include "attn_rel.hpp"
+#include "attn_rel_mfma.hpp"
 #include "launchers.hpp"
 
 namespace gn {
@@ -36,46 +36,6 @@ constexpr int RM_G = 16;                           // heads per workgroup = M of
 constexpr int RM_ROWS = 32;                        // rows a workgroup owns: half a tile of the plan
 constexpr int RM_KB = 16;                          // rows of the other side per block
 constexpr int RM_NT = 512;                         // threads: one pair of a block each
-
-typedef short rm_s16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) rm_s16x4 rm_lds_s16x4;
-
-__device__ __forceinline__ float rm_exp2(float x) { return __builtin_amdgcn_exp2f(x); }       // bare v_exp_f32: exp2(-inf) = 0
-__device__ __forceinline__ f32x4 rm_mma32(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ f32x4 rm_mma16(rm_s16x4 a, rm_s16x4 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ void rm_zero(f32x4& a) { a = f32x4{0.0f, 0.0f, 0.0f, 0.0f}; }       // (common.hpp's zero_acc is for 16 registers)
-__device__ __forceinline__ bf16x8 rm_ld8(const __bf16* p) { return *reinterpret_cast<const bf16x8*>(p); }
-__device__ __forceinline__ rm_s16x4 rm_pack4(float a, float b, float c, float d) {
-    bf16x4 v;
-    v[0] = (__bf16)a; v[1] = (__bf16)b; v[2] = (__bf16)c; v[3] = (__bf16)d;
-    return __builtin_bit_cast(rm_s16x4, v);
-}
-__device__ __forceinline__ void rm_store4(__bf16* p, float a, float b, float c, float d) {
-    *reinterpret_cast<rm_s16x4*>(p) = rm_pack4(a, b, c, d);
-}
-// 16x16x16 operand (A: row = l & 15, B: column = l & 15; k = 4 (l >> 4) .. + 3) TRANSPOSED out of a row-major bf16 tile: element
-// (k, col0 + (l & 15)) of the tile at `tile` with `pitch` elements per row.  The 16 lanes of a group address the 4 rows x 16 columns
-// they share, lane (l & 15) the 4 columns 4 (l & 3) .. of row (l & 15) >> 2, and each receives the 4 rows of its own column.
-__device__ __forceinline__ rm_s16x4 rm_tr(const __bf16* tile, int pitch, int col0, int lane) {
-    const int li = lane & 15, g4 = lane >> 4;
-    const __bf16* p = tile + (4 * g4 + (li >> 2)) * pitch + col0 + 4 * (li & 3);
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((rm_lds_s16x4*)(p));
-}
-
-// frequencies in revolutions per unit, hi + lo, wave-uniform (the arithmetic of attn_rel.hip's rel_freq_table)
-__device__ __forceinline__ void rm_freq_table(const float* __restrict__ freq, int lane, float (&ghi)[RM_HF], float (&glo)[RM_HF]) {
-    float hi_l = 0.0f, lo_l = 0.0f;
-    if (lane < RM_HF) {
-        const double g = (double)freq[lane] * 0.15915494309189534561;
-        hi_l = (float)g;
-        lo_l = (float)(g - (double)hi_l);
-    }
-#pragma unroll
-    for (int k = 0; k < RM_HF; ++k) {
-        ghi[k] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, hi_l), k));
-        glo[k] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, lo_l), k));
-    }
-}
 
 // s_ij = [sin | cos] of pair argument a, each value rounded once to bf16 -> the pair's 32 columns at dst (64 bytes)
 __device__ __forceinline__ void rm_produce(__bf16* __restrict__ dst, float a, const float (&ghi)[RM_HF], const float (&glo)[RM_HF]) {
@@ -113,11 +73,8 @@ __device__ __forceinline__ void rm_put(__bf16* __restrict__ dst, const bf16x8 (&
 #define RM_PROLOGUE                                                                                             \
     const int tile = blockIdx.x >> 1, tid = threadIdx.x, lane = tid & 63;                                       \
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);                                                  \
-    if (tile >= tile_ptr[B]) return;                          /* blockIdx.x alone: the whole workgroup leaves */ \
-    const int es = rel_event_of_tile(tile_ptr, B, tile);                                                        \
-    const int e = tile_ptr[B + 1 + es];                                                                         \
-    const int kbeg = ptr[e], kend = ptr[e + 1];                                                                 \
-    const int r0 = kbeg + (tile - tile_ptr[es]) * REL_TILE + RM_ROWS * (int)(blockIdx.x & 1);                   \
+    REL_EVENT_PROLOGUE(t0)                                                                                      \
+    const int r0 = t0 + RM_ROWS * (int)(blockIdx.x & 1);                                                        \
     if (r0 >= kend) return;                                   /* the tile's second half lies past the event */  \
     const int E = H * RM_DH, li = lane & 15, g4 = lane >> 4;                                                    \
     const int head0 = blockIdx.y * RM_G;                                                                        \
@@ -148,7 +105,7 @@ __global__ __launch_bounds__(RM_NT) void rel_attn_mfma_fwd_kernel(
     float* const Cs = reinterpret_cast<float*>(rm_lds + RM_B_S + RM_B_X + RM_B_P + 2 * RM_B_R);   // [32 q][16 head]
     RM_PROLOGUE
     float ghi[RM_HF], glo[RM_HF];
-    rm_freq_table(freq, lane, ghi, glo);
+    rel_freq_table<RM_HF>(freq, 0, lane, ghi, glo);
     const int pq = tid >> 4, pk = tid & 15;                    // the pair this thread forms s_ij of
     const float4 xi = rel_load_xt(xt, ldxt, min(r0 + pq, kend - 1));
     // per query: q' of queries 4 w + t, row = head li of the group
@@ -281,30 +238,6 @@ __global__ __launch_bounds__(RM_NT) void rel_attn_mfma_fwd_kernel(
     }
 }
 
-// delta[i, h] = dU_i . U_i + dO_i . O_i (fp32, one thread per (row, head)) for both backward passes
-__global__ __launch_bounds__(256) void rel_attn_mfma_delta_kernel(
-    const __bf16* __restrict__ out, long long ldo, const __bf16* __restrict__ u, long long ldu, const __bf16* __restrict__ dout,
-    long long lddo, const __bf16* __restrict__ du, long long lddu, int H, long long NH, float* __restrict__ delta) {
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= NH) return;
-    const long long row = idx / H;
-    const int col = (int)(idx % H) * RM_DH;
-    float dl = 0.0f;
-#pragma unroll
-    for (int c8 = 0; c8 < RM_DH / 8; ++c8) {
-        const bf16x8 a = rm_ld8(du + row * lddu + col + 8 * c8), b = rm_ld8(u + row * ldu + col + 8 * c8);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) dl = fmaf((float)a[i], (float)b[i], dl);
-    }
-#pragma unroll
-    for (int c8 = 0; c8 < RM_DH / 8; ++c8) {
-        const bf16x8 a = rm_ld8(dout + row * lddo + col + 8 * c8), b = rm_ld8(out + row * ldo + col + 8 * c8);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) dl = fmaf((float)a[i], (float)b[i], dl);
-    }
-    delta[idx] = dl;
-}
-
 // dQ / dQ' pass: the workgroup owns 32 queries.  As the forward with two per-query products before the per-head step (bias and
 // the bias part of dA) and dS in the place of P; scores are recomputed from lse2, nothing is rescaled.
 __global__ __launch_bounds__(RM_NT) void rel_attn_mfma_bwd_dq_kernel(
@@ -322,7 +255,7 @@ __global__ __launch_bounds__(RM_NT) void rel_attn_mfma_bwd_dq_kernel(
     __bf16* const Vs = Ks + RM_B_R / 2;
     RM_PROLOGUE
     float ghi[RM_HF], glo[RM_HF];
-    rm_freq_table(freq, lane, ghi, glo);
+    rel_freq_table<RM_HF>(freq, 0, lane, ghi, glo);
     const int pq = tid >> 4, pk = tid & 15;
     const float4 xi = rel_load_xt(xt, ldxt, min(r0 + pq, kend - 1));
     const float scale2 = scale * REL_LOG2E;
@@ -465,7 +398,7 @@ __global__ __launch_bounds__(RM_NT) void rel_attn_mfma_bwd_dkv_kernel(
     float* const Ds = Ls + RM_KB * RM_G;
     RM_PROLOGUE
     float ghi[RM_HF], glo[RM_HF];
-    rm_freq_table(freq, lane, ghi, glo);
+    rel_freq_table<RM_HF>(freq, 0, lane, ghi, glo);
     const int pq = tid >> 5, pk = tid & 31;                    // the pair this thread forms s_ij of: query of the block, key
     const float4 xj = rel_load_xt(xt, ldxt, min(r0 + pk, kend - 1));
     const float scale2 = scale * REL_LOG2E;
@@ -594,27 +527,17 @@ __global__ __launch_bounds__(RM_NT) void rel_attn_mfma_bwd_dkv_kernel(
 
 bool rel_attn_mfma_supported(int DH) { return DH == RM_DH; }
 
-// more than 64 KB of dynamic LDS has to be asked for once per kernel
-template <typename K>
-static hipError_t rm_allow_lds(K kernel, int bytes) {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-}
-
 hipError_t launch_rel_attn_mfma_fwd(const void* qkv, long long ld, const void* qp, long long ldqp, const float* xt, long long ldxt,
                                     const float* freq, int H, int DH, const int* ptr, const int* tile_ptr, int B, int N, void* out,
                                     long long ldo, void* u, long long ldu, float* lse2, hipStream_t st) {
-    const long long d = (long long)H * DH;
-    if (!rel_attn_mfma_supported(DH) || ld % 8 || ldqp % 8 || ldo % 8 || ldu % 8 || ldxt < 4 || ld < 3 * d || ldqp < d || ldo < d ||
-        ldu < d)
-        return hipErrorInvalidValue;
+    if (!rel_attn_mfma_supported(DH) || !rel_args_ok(false, 8, H, DH, ld, ldqp, ldxt, ldo, ldu)) return hipErrorInvalidValue;
     if (N == 0 || B == 0) return hipSuccess;
-    static const hipError_t once = rm_allow_lds(&rel_attn_mfma_fwd_kernel, RM_LDS_FWD);
+    static const hipError_t once = rel_allow_lds(&rel_attn_mfma_fwd_kernel, RM_LDS_FWD);
     if (once != hipSuccess) return once;
     const dim3 grid(2u * (unsigned)(N / REL_TILE + B), (unsigned)((H + RM_G - 1) / RM_G)), block(RM_NT);
-    const float scale2 = REL_LOG2E / sqrtf((float)DH);
     hipLaunchKernelGGL(rel_attn_mfma_fwd_kernel, grid, block, RM_LDS_FWD, st, static_cast<const __bf16*>(qkv), ld,
-                       static_cast<const __bf16*>(qp), ldqp, xt, ldxt, freq, H, ptr, tile_ptr, B, scale2, static_cast<__bf16*>(out), ldo,
-                       static_cast<__bf16*>(u), ldu, lse2);
+                       static_cast<const __bf16*>(qp), ldqp, xt, ldxt, freq, H, ptr, tile_ptr, B, rel_scale2(DH),
+                       static_cast<__bf16*>(out), ldo, static_cast<__bf16*>(u), ldu, lse2);
     return hipGetLastError();
 }
 
@@ -623,13 +546,11 @@ hipError_t launch_rel_attn_mfma_bwd(const void* qkv, long long ld, const void* q
                                     const void* out, long long ldo, const void* u, long long ldu, const void* dout, long long lddo,
                                     const void* du, long long lddu, const float* lse2, float* delta, void* dqkv, long long lddq,
                                     void* dqp, long long lddqp, hipStream_t st) {
-    const long long d = (long long)H * DH;
-    if (!rel_attn_mfma_supported(DH) || ld % 8 || ldqp % 8 || ldo % 8 || ldu % 8 || lddo % 8 || lddu % 8 || lddq % 8 || lddqp % 8 ||
-        ldxt < 4 || ld < 3 * d || lddq < 3 * d || ldqp < d || ldo < d || ldu < d || lddo < d || lddu < d || lddqp < d)
+    if (!rel_attn_mfma_supported(DH) || !rel_args_ok(true, 8, H, DH, ld, ldqp, ldxt, ldo, ldu, lddo, lddu, lddq, lddqp))
         return hipErrorInvalidValue;
     if (N == 0 || B == 0) return hipSuccess;
-    static const hipError_t once_dq = rm_allow_lds(&rel_attn_mfma_bwd_dq_kernel, RM_LDS_DQ);
-    static const hipError_t once_kv = rm_allow_lds(&rel_attn_mfma_bwd_dkv_kernel, RM_LDS_KV);
+    static const hipError_t once_dq = rel_allow_lds(&rel_attn_mfma_bwd_dq_kernel, RM_LDS_DQ);
+    static const hipError_t once_kv = rel_allow_lds(&rel_attn_mfma_bwd_dkv_kernel, RM_LDS_KV);
     if (once_dq != hipSuccess) return once_dq;
     if (once_kv != hipSuccess) return once_kv;
     const __bf16* qkv_ = static_cast<const __bf16*>(qkv);
@@ -637,10 +558,10 @@ hipError_t launch_rel_attn_mfma_bwd(const void* qkv, long long ld, const void* q
     const __bf16* dout_ = static_cast<const __bf16*>(dout);
     const __bf16* du_ = static_cast<const __bf16*>(du);
     const long long NH = (long long)N * H;
-    hipLaunchKernelGGL(rel_attn_mfma_delta_kernel, dim3((unsigned)((NH + 255) / 256)), dim3(256), 0, st,
+    hipLaunchKernelGGL(rel_attn_mfma_delta_kernel<RM_DH>, dim3((unsigned)((NH + 255) / 256)), dim3(256), 0, st,
                        static_cast<const __bf16*>(out), ldo, static_cast<const __bf16*>(u), ldu, dout_, lddo, du_, lddu, H, NH, delta);
     const dim3 grid(2u * (unsigned)(N / REL_TILE + B), (unsigned)((H + RM_G - 1) / RM_G)), block(RM_NT);
-    const float scale = 1.0f / sqrtf((float)DH);
+    const float scale = rel_scale(DH);
     hipLaunchKernelGGL(rel_attn_mfma_bwd_dq_kernel, grid, block, RM_LDS_DQ, st, qkv_, ld, qp_, ldqp, xt, ldxt, freq, H, ptr, tile_ptr,
                        B, scale, dout_, lddo, du_, lddu, lse2, delta, static_cast<__bf16*>(dqkv), lddq, static_cast<__bf16*>(dqp), lddqp);
     hipLaunchKernelGGL(rel_attn_mfma_bwd_dkv_kernel, grid, block, RM_LDS_KV, st, qkv_, ld, qp_, ldqp, xt, ldxt, freq, H, ptr,

@@ -28,7 +28,7 @@
 // head, the row or the lane.  Heads past H - 1 compute on head H - 1 and rows past the event on its last row (every load is
 // clamped), and store nothing.  The two `return`s depend on blockIdx.x and the event alone: a workgroup leaves as a whole
 // before its first barrier.  No atomics; no packed fp32 operations.
-#include "attn_rel.hpp"
+#include "attn_rel_mfma.hpp"
 #include "launchers.hpp"
 
 namespace gn {
@@ -42,56 +42,17 @@ constexpr int RX_NT = 512;                         // threads: two per pair of a
 constexpr int RX_NC = RX_DH / 16;                  // 16-wide column tiles of a head
 constexpr int RX_PC = RX_KB * RX_G * RX_DH / 8 / RX_NT;   // 16-byte pieces of a staged block per thread
 
-typedef short rx_s16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) rx_s16x4 rx_lds_s16x4;
-
-__device__ __forceinline__ float rx_exp2(float x) { return __builtin_amdgcn_exp2f(x); }       // bare v_exp_f32: exp2(-inf) = 0
-__device__ __forceinline__ f32x4 rx_mma32(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ f32x4 rx_mma16(rx_s16x4 a, rx_s16x4 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ void rx_zero(f32x4& a) { a = f32x4{0.0f, 0.0f, 0.0f, 0.0f}; }       // (common.hpp's zero_acc is for 16 registers)
-__device__ __forceinline__ bf16x8 rx_ld8(const __bf16* p) { return *reinterpret_cast<const bf16x8*>(p); }
 // the two k halves (columns 32 kh + 8 (l >> 4) .. + 7) of a 64-wide row as the operands of two 16x16x32 products
 __device__ __forceinline__ void rx_ld64(bf16x8 (&r)[2], const __bf16* p, int g4) {
-    r[0] = rx_ld8(p + 8 * g4);
-    r[1] = rx_ld8(p + 32 + 8 * g4);
+    r[0] = rm_ld8(p + 8 * g4);
+    r[1] = rm_ld8(p + 32 + 8 * g4);
 }
 // a[16 x 64] b[16 x 64]^T: the 16x16 tile over the whole head width
 __device__ __forceinline__ f32x4 rx_dot64(const bf16x8 (&a)[2], const bf16x8 (&b)[2]) {
     f32x4 c;
-    rx_zero(c);
-    c = rx_mma32(a[0], b[0], c);
-    return rx_mma32(a[1], b[1], c);
-}
-__device__ __forceinline__ rx_s16x4 rx_pack4(float a, float b, float c, float d) {
-    bf16x4 v;
-    v[0] = (__bf16)a; v[1] = (__bf16)b; v[2] = (__bf16)c; v[3] = (__bf16)d;
-    return __builtin_bit_cast(rx_s16x4, v);
-}
-__device__ __forceinline__ void rx_store4(__bf16* p, float a, float b, float c, float d) {
-    *reinterpret_cast<rx_s16x4*>(p) = rx_pack4(a, b, c, d);
-}
-// 16x16x16 operand (A: row = l & 15, B: column = l & 15; k = 4 (l >> 4) .. + 3) TRANSPOSED out of a row-major bf16 tile: element
-// (k, col0 + (l & 15)) of the tile at `tile` with `pitch` elements per row.  The 16 lanes of a group address the 4 rows x 16 columns
-// they share, lane (l & 15) the 4 columns 4 (l & 3) .. of row (l & 15) >> 2, and each receives the 4 rows of its own column.
-__device__ __forceinline__ rx_s16x4 rx_tr(const __bf16* tile, int pitch, int col0, int lane) {
-    const int li = lane & 15, g4 = lane >> 4;
-    const __bf16* p = tile + (4 * g4 + (li >> 2)) * pitch + col0 + 4 * (li & 3);
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((rx_lds_s16x4*)(p));
-}
-
-// frequencies [16 fh, 16 fh + 16) in revolutions per unit, hi + lo, wave-uniform (the arithmetic of attn_rel_wide.hip's rw_freq_table)
-__device__ __forceinline__ void rx_freq_table(const float* __restrict__ freq, int fh, int lane, float (&ghi)[RX_HF], float (&glo)[RX_HF]) {
-    float hi_l = 0.0f, lo_l = 0.0f;
-    if (lane < RX_HF) {
-        const double g = (double)freq[RX_HF * fh + lane] * 0.15915494309189534561;
-        hi_l = (float)g;
-        lo_l = (float)(g - (double)hi_l);
-    }
-#pragma unroll
-    for (int k = 0; k < RX_HF; ++k) {
-        ghi[k] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, hi_l), k));
-        glo[k] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, lo_l), k));
-    }
+    rm_zero(c);
+    c = rm_mma32(a[0], b[0], c);
+    return rm_mma32(a[1], b[1], c);
 }
 
 // this thread's half of s_ij = [32 sines | 32 cosines] of pair argument a, each value rounded once to bf16: sines to columns
@@ -119,7 +80,7 @@ __device__ __forceinline__ void rx_fetch(bf16x8 (&r)[RX_PC], const __bf16* __res
     for (int it = 0; it < RX_PC; ++it) {
         const int idx = it * RX_NT + tid;
         const int row = min(row0 + (idx >> 7), r_last), hh = min(head0 + ((idx >> 3) & 15), H - 1);
-        r[it] = rx_ld8(src + (long long)row * ld + col0 + hh * RX_DH + (idx & 7) * 8);
+        r[it] = rm_ld8(src + (long long)row * ld + col0 + hh * RX_DH + (idx & 7) * 8);
     }
 }
 __device__ __forceinline__ void rx_put(__bf16* __restrict__ dst, const bf16x8 (&r)[RX_PC], int tid) {
@@ -132,18 +93,15 @@ __device__ __forceinline__ void rx_put(__bf16* __restrict__ dst, const bf16x8 (&
 #define RX_PROLOGUE                                                                                             \
     const int tile = blockIdx.x >> 2, tid = threadIdx.x, lane = tid & 63;                                       \
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);                                                  \
-    if (tile >= tile_ptr[B]) return;                          /* blockIdx.x alone: the whole workgroup leaves */ \
-    const int es = rel_event_of_tile(tile_ptr, B, tile);                                                        \
-    const int e = tile_ptr[B + 1 + es];                                                                         \
-    const int kbeg = ptr[e], kend = ptr[e + 1];                                                                 \
-    const int r0 = kbeg + (tile - tile_ptr[es]) * REL_TILE + RX_ROWS * (int)(blockIdx.x & 3);                   \
+    REL_EVENT_PROLOGUE(t0)                                                                                      \
+    const int r0 = t0 + RX_ROWS * (int)(blockIdx.x & 3);                                                        \
     if (r0 >= kend) return;                                   /* this quarter of the tile lies past the event */ \
     const int E = H * RX_DH, li = lane & 15, g4 = lane >> 4;                                                    \
     const int head0 = blockIdx.y * RX_G;                                                                        \
     const int nb = (kend - kbeg + RX_KB - 1) / RX_KB;         /* blocks of the event: the same for every thread */ \
     const int fh = wave >> 2, pa = (tid >> 4) & 15, pb = tid & 15;                                              \
     float ghi[RX_HF], glo[RX_HF];                                                                               \
-    rx_freq_table(freq, fh, lane, ghi, glo);
+    rel_freq_table<RX_HF>(freq, fh, lane, ghi, glo);
 
 // LDS, bytes.  forward: s_ij, X, P, K, V, corr;  dQ pass: s_ij, X, Y, dS, K, V;  dK / dV pass: s_ij, X, Y, Q, dO, lse2, delta
 constexpr int RX_B_S = RX_ROWS * RX_KB * RX_DH * 2;        // 32 KB  s_ij of a block, bf16 [row][row of the other side][64]
@@ -180,7 +138,7 @@ __global__ __launch_bounds__(RX_NT) void rel_attn_mfma_wide_fwd_kernel(
     for (int t = 0; t < 2; ++t) {
         rx_ld64(qpf[t], qp + (long long)min(r0 + 2 * wave + t, kend - 1) * ldqp + min(head0 + li, H - 1) * RX_DH, g4);
 #pragma unroll
-        for (int n = 0; n < RX_NC; ++n) rx_zero(uu[t][n]);
+        for (int n = 0; n < RX_NC; ++n) rm_zero(uu[t][n]);
     }
     // per head: q of heads 2 w + j, column = query li
     bf16x8 qf[2][2];
@@ -190,7 +148,7 @@ __global__ __launch_bounds__(RX_NT) void rel_attn_mfma_wide_fwd_kernel(
     for (int j = 0; j < 2; ++j) {
         rx_ld64(qf[j], qkv + (long long)min(r0 + li, kend - 1) * ld + min(head0 + 2 * wave + j, H - 1) * RX_DH, g4);
 #pragma unroll
-        for (int n = 0; n < RX_NC; ++n) rx_zero(o[j][n]);
+        for (int n = 0; n < RX_NC; ++n) rm_zero(o[j][n]);
         m[j] = -INFINITY; l[j] = 0.0f;
     }
     bf16x8 kn[RX_PC], vn[RX_PC];
@@ -232,20 +190,20 @@ __global__ __launch_bounds__(RX_NT) void rel_attn_mfma_wide_fwd_kernel(
             mx = fmaxf(mx, __shfl_xor(mx, 16));
             mx = fmaxf(mx, __shfl_xor(mx, 32));
             const float mn = fmaxf(m[j], mx);                 // finite: key kb of every block exists
-            const float corr = rx_exp2(m[j] - mn);
+            const float corr = rm_exp2(m[j] - mn);
             float p[4];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) p[r] = rx_exp2(sc[r] - mn);
+            for (int r = 0; r < 4; ++r) p[r] = rm_exp2(sc[r] - mn);
             l[j] = fmaf(l[j], corr, (p[0] + p[1]) + (p[2] + p[3]));      // this lane's 4 keys; summed over g4 at the end
             m[j] = mn;
-            const rx_s16x4 pv = rx_pack4(p[0], p[1], p[2], p[3]);
-            *reinterpret_cast<rx_s16x4*>(Ps + (q * RX_G + hl) * RX_KB + 4 * g4) = pv;
+            const rm_s16x4 pv = rm_pack4(p[0], p[1], p[2], p[3]);
+            *reinterpret_cast<rm_s16x4*>(Ps + (q * RX_G + hl) * RX_KB + 4 * g4) = pv;
             if (g4 == 0) Cs[q * RX_G + hl] = corr;
 #pragma unroll
             for (int n = 0; n < RX_NC; ++n) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) o[j][n][r] *= corr;
-                o[j][n] = rx_mma16(rx_tr(Vs, RX_G * RX_DH, hl * RX_DH + 16 * n, lane), pv, o[j][n]);   // O^T[d 16 n + 4 g4 + r][query li]
+                o[j][n] = rm_mma16(rm_tr(Vs, RX_G * RX_DH, hl * RX_DH + 16 * n, lane), pv, o[j][n]);   // O^T[d 16 n + 4 g4 + r][query li]
             }
         }
         __syncthreads();                                      // D: P and the rescale factors are in LDS
@@ -253,11 +211,11 @@ __global__ __launch_bounds__(RX_NT) void rel_attn_mfma_wide_fwd_kernel(
         for (int t = 0; t < 2; ++t) {                         // U_i[head 4 g4 + r][c 16 n + li] of query 2 w + t
             const int q = 2 * wave + t;
             const float4 c = *reinterpret_cast<const float4*>(Cs + q * RX_G + 4 * g4);
-            const rx_s16x4 pw = *reinterpret_cast<const rx_s16x4*>(Ps + (q * RX_G + li) * RX_KB + 4 * g4);
+            const rm_s16x4 pw = *reinterpret_cast<const rm_s16x4*>(Ps + (q * RX_G + li) * RX_KB + 4 * g4);
 #pragma unroll
             for (int n = 0; n < RX_NC; ++n) {
                 uu[t][n][0] *= c.x; uu[t][n][1] *= c.y; uu[t][n][2] *= c.z; uu[t][n][3] *= c.w;
-                uu[t][n] = rx_mma16(pw, rx_tr(Ss + q * RX_KB * RX_DH, RX_DH, 16 * n, lane), uu[t][n]);
+                uu[t][n] = rm_mma16(pw, rm_tr(Ss + q * RX_KB * RX_DH, RX_DH, 16 * n, lane), uu[t][n]);
             }
         }
     }
@@ -273,7 +231,7 @@ __global__ __launch_bounds__(RX_NT) void rel_attn_mfma_wide_fwd_kernel(
         if (qi < kend && head < H) {
 #pragma unroll
             for (int n = 0; n < RX_NC; ++n)
-                rx_store4(out + (long long)qi * ldo + head * RX_DH + 16 * n + 4 * g4, o[j][n][0] * inv, o[j][n][1] * inv,
+                rm_store4(out + (long long)qi * ldo + head * RX_DH + 16 * n + 4 * g4, o[j][n][0] * inv, o[j][n][1] * inv,
                           o[j][n][2] * inv, o[j][n][3] * inv);
             if (g4 == 0) lse2[(long long)qi * H + head] = m[j] + log2f(lt);
         }
@@ -293,30 +251,6 @@ __global__ __launch_bounds__(RX_NT) void rel_attn_mfma_wide_fwd_kernel(
             }
         }
     }
-}
-
-// delta[i, h] = dU_i . U_i + dO_i . O_i (fp32, one thread per (row, head)) for both backward passes
-__global__ __launch_bounds__(256) void rel_attn_mfma_wide_delta_kernel(
-    const __bf16* __restrict__ out, long long ldo, const __bf16* __restrict__ u, long long ldu, const __bf16* __restrict__ dout,
-    long long lddo, const __bf16* __restrict__ du, long long lddu, int H, long long NH, float* __restrict__ delta) {
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= NH) return;
-    const long long row = idx / H;
-    const int col = (int)(idx % H) * RX_DH;
-    float dl = 0.0f;
-#pragma unroll
-    for (int c8 = 0; c8 < RX_DH / 8; ++c8) {
-        const bf16x8 a = rx_ld8(du + row * lddu + col + 8 * c8), b = rx_ld8(u + row * ldu + col + 8 * c8);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) dl = fmaf((float)a[i], (float)b[i], dl);
-    }
-#pragma unroll
-    for (int c8 = 0; c8 < RX_DH / 8; ++c8) {
-        const bf16x8 a = rx_ld8(dout + row * lddo + col + 8 * c8), b = rx_ld8(out + row * ldo + col + 8 * c8);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) dl = fmaf((float)a[i], (float)b[i], dl);
-    }
-    delta[idx] = dl;
 }
 
 // dQ / dQ' pass: the workgroup owns 16 queries.  As the forward with two per-query products before the per-head step (bias and
@@ -346,7 +280,7 @@ __global__ __launch_bounds__(RX_NT) void rel_attn_mfma_wide_bwd_dq_kernel(
         rx_ld64(qpf[t], qp + row * ldqp + col, g4);
         rx_ld64(duf[t], du + row * lddu + col, g4);
 #pragma unroll
-        for (int n = 0; n < RX_NC; ++n) rx_zero(dqq[t][n]);
+        for (int n = 0; n < RX_NC; ++n) rm_zero(dqq[t][n]);
     }
     bf16x8 qf[2][2], gf[2][2];
     f32x4 dq[2][RX_NC];
@@ -360,7 +294,7 @@ __global__ __launch_bounds__(RX_NT) void rel_attn_mfma_wide_bwd_dq_kernel(
         ls[j] = lse2[row * H + hc];
         dl[j] = delta[row * H + hc];
 #pragma unroll
-        for (int n = 0; n < RX_NC; ++n) rx_zero(dq[j][n]);
+        for (int n = 0; n < RX_NC; ++n) rm_zero(dq[j][n]);
     }
     bf16x8 kn[RX_PC], vn[RX_PC];
     rx_fetch(kn, qkv, ld, E, head0, H, kbeg, kend - 1, tid);
@@ -403,23 +337,23 @@ __global__ __launch_bounds__(RX_NT) void rel_attn_mfma_wide_bwd_dq_kernel(
             float dS[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                float p = rx_exp2(fmaf(s[r], scale2, xs[r]) - ls[j]);
+                float p = rm_exp2(fmaf(s[r], scale2, xs[r]) - ls[j]);
                 if (kb + 4 * g4 + r >= kend) p = 0.0f;
                 dS[r] = p * ((dp[r] + ys[r]) - dl[j]);
             }
-            const rx_s16x4 db = rx_pack4(dS[0], dS[1], dS[2], dS[3]);
-            *reinterpret_cast<rx_s16x4*>(Ps + (q * RX_G + hl) * RX_KB + 4 * g4) = db;
+            const rm_s16x4 db = rm_pack4(dS[0], dS[1], dS[2], dS[3]);
+            *reinterpret_cast<rm_s16x4*>(Ps + (q * RX_G + hl) * RX_KB + 4 * g4) = db;
 #pragma unroll
             for (int n = 0; n < RX_NC; ++n)                   // dq^T[d 16 n + 4 g4 + r][query li]
-                dq[j][n] = rx_mma16(rx_tr(Ks, RX_G * RX_DH, hl * RX_DH + 16 * n, lane), db, dq[j][n]);
+                dq[j][n] = rm_mma16(rm_tr(Ks, RX_G * RX_DH, hl * RX_DH + 16 * n, lane), db, dq[j][n]);
         }
         __syncthreads();                                      // D
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             const int q = 2 * wave + t;
-            const rx_s16x4 pw = *reinterpret_cast<const rx_s16x4*>(Ps + (q * RX_G + li) * RX_KB + 4 * g4);
+            const rm_s16x4 pw = *reinterpret_cast<const rm_s16x4*>(Ps + (q * RX_G + li) * RX_KB + 4 * g4);
 #pragma unroll
-            for (int n = 0; n < RX_NC; ++n) dqq[t][n] = rx_mma16(pw, rx_tr(Ss + q * RX_KB * RX_DH, RX_DH, 16 * n, lane), dqq[t][n]);
+            for (int n = 0; n < RX_NC; ++n) dqq[t][n] = rm_mma16(pw, rm_tr(Ss + q * RX_KB * RX_DH, RX_DH, 16 * n, lane), dqq[t][n]);
         }
     }
 #pragma unroll
@@ -428,7 +362,7 @@ __global__ __launch_bounds__(RX_NT) void rel_attn_mfma_wide_bwd_dq_kernel(
         if (qi < kend && head < H) {
 #pragma unroll
             for (int n = 0; n < RX_NC; ++n)
-                rx_store4(dqkv + (long long)qi * lddq + head * RX_DH + 16 * n + 4 * g4, dq[j][n][0] * scale, dq[j][n][1] * scale,
+                rm_store4(dqkv + (long long)qi * lddq + head * RX_DH + 16 * n + 4 * g4, dq[j][n][0] * scale, dq[j][n][1] * scale,
                           dq[j][n][2] * scale, dq[j][n][3] * scale);
         }
     }
@@ -478,7 +412,7 @@ __global__ __launch_bounds__(RX_NT) void rel_attn_mfma_wide_bwd_dkv_kernel(
         rx_ld64(kf[j], qkv + row * ld + E + hc * RX_DH, g4);
         rx_ld64(vf[j], qkv + row * ld + 2 * E + hc * RX_DH, g4);
 #pragma unroll
-        for (int n = 0; n < RX_NC; ++n) { rx_zero(dk[j][n]); rx_zero(dv[j][n]); }
+        for (int n = 0; n < RX_NC; ++n) { rm_zero(dk[j][n]); rm_zero(dv[j][n]); }
     }
     // lse2 / delta of (query, head) = (pa, pb) of the block, by the first 256 threads (the others load the same again)
     const int sh = min(head0 + pb, H - 1);
@@ -535,15 +469,15 @@ __global__ __launch_bounds__(RX_NT) void rel_attn_mfma_wide_bwd_dkv_kernel(
             float p[4], dS[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                p[r] = rx_exp2(fmaf(s[r], scale2, xs[r]) - Ls[(4 * g4 + r) * RX_G + hl]);
+                p[r] = rm_exp2(fmaf(s[r], scale2, xs[r]) - Ls[(4 * g4 + r) * RX_G + hl]);
                 if (qb + 4 * g4 + r >= kend) p[r] = 0.0f;
                 dS[r] = p[r] * ((dp[r] + ys[r]) - Ds[(4 * g4 + r) * RX_G + hl]);
             }
-            const rx_s16x4 pv = rx_pack4(p[0], p[1], p[2], p[3]), db = rx_pack4(dS[0], dS[1], dS[2], dS[3]);
+            const rm_s16x4 pv = rm_pack4(p[0], p[1], p[2], p[3]), db = rm_pack4(dS[0], dS[1], dS[2], dS[3]);
 #pragma unroll
             for (int n = 0; n < RX_NC; ++n) {                 // dv^T, dk^T[d 16 n + 4 g4 + r][key li]
-                dv[j][n] = rx_mma16(rx_tr(Gs, RX_G * RX_DH, hl * RX_DH + 16 * n, lane), pv, dv[j][n]);
-                dk[j][n] = rx_mma16(rx_tr(Qs, RX_G * RX_DH, hl * RX_DH + 16 * n, lane), db, dk[j][n]);
+                dv[j][n] = rm_mma16(rm_tr(Gs, RX_G * RX_DH, hl * RX_DH + 16 * n, lane), pv, dv[j][n]);
+                dk[j][n] = rm_mma16(rm_tr(Qs, RX_G * RX_DH, hl * RX_DH + 16 * n, lane), db, dk[j][n]);
             }
         }
     }
@@ -553,9 +487,9 @@ __global__ __launch_bounds__(RX_NT) void rel_attn_mfma_wide_bwd_dkv_kernel(
         if (kj < kend && head < H) {
 #pragma unroll
             for (int n = 0; n < RX_NC; ++n) {
-                rx_store4(dqkv + (long long)kj * lddq + E + head * RX_DH + 16 * n + 4 * g4, dk[j][n][0] * scale, dk[j][n][1] * scale,
+                rm_store4(dqkv + (long long)kj * lddq + E + head * RX_DH + 16 * n + 4 * g4, dk[j][n][0] * scale, dk[j][n][1] * scale,
                           dk[j][n][2] * scale, dk[j][n][3] * scale);
-                rx_store4(dqkv + (long long)kj * lddq + 2 * E + head * RX_DH + 16 * n + 4 * g4, dv[j][n][0], dv[j][n][1], dv[j][n][2],
+                rm_store4(dqkv + (long long)kj * lddq + 2 * E + head * RX_DH + 16 * n + 4 * g4, dv[j][n][0], dv[j][n][1], dv[j][n][2],
                           dv[j][n][3]);
             }
         }
@@ -565,27 +499,17 @@ __global__ __launch_bounds__(RX_NT) void rel_attn_mfma_wide_bwd_dkv_kernel(
 
 bool rel_attn_mfma_wide_supported(int DH) { return DH == RX_DH; }
 
-// more than 64 KB of dynamic LDS has to be asked for once per kernel
-template <typename K>
-static hipError_t rx_allow_lds(K kernel, int bytes) {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-}
-
 hipError_t launch_rel_attn_mfma_wide_fwd(const void* qkv, long long ld, const void* qp, long long ldqp, const float* xt,
                                          long long ldxt, const float* freq, int H, int DH, const int* ptr, const int* tile_ptr, int B,
                                          int N, void* out, long long ldo, void* u, long long ldu, float* lse2, hipStream_t st) {
-    const long long d = (long long)H * DH;
-    if (!rel_attn_mfma_wide_supported(DH) || ld % 8 || ldqp % 8 || ldo % 8 || ldu % 8 || ldxt < 4 || ld < 3 * d || ldqp < d ||
-        ldo < d || ldu < d)
-        return hipErrorInvalidValue;
+    if (!rel_attn_mfma_wide_supported(DH) || !rel_args_ok(false, 8, H, DH, ld, ldqp, ldxt, ldo, ldu)) return hipErrorInvalidValue;
     if (N == 0 || B == 0) return hipSuccess;
-    static const hipError_t once = rx_allow_lds(&rel_attn_mfma_wide_fwd_kernel, RX_LDS_FWD);
+    static const hipError_t once = rel_allow_lds(&rel_attn_mfma_wide_fwd_kernel, RX_LDS_FWD);
     if (once != hipSuccess) return once;
     const dim3 grid((unsigned)(REL_TILE / RX_ROWS) * (unsigned)(N / REL_TILE + B), (unsigned)((H + RX_G - 1) / RX_G)), block(RX_NT);
-    const float scale2 = REL_LOG2E / sqrtf((float)DH);
     hipLaunchKernelGGL(rel_attn_mfma_wide_fwd_kernel, grid, block, RX_LDS_FWD, st, static_cast<const __bf16*>(qkv), ld,
-                       static_cast<const __bf16*>(qp), ldqp, xt, ldxt, freq, H, ptr, tile_ptr, B, scale2, static_cast<__bf16*>(out), ldo,
-                       static_cast<__bf16*>(u), ldu, lse2);
+                       static_cast<const __bf16*>(qp), ldqp, xt, ldxt, freq, H, ptr, tile_ptr, B, rel_scale2(DH),
+                       static_cast<__bf16*>(out), ldo, static_cast<__bf16*>(u), ldu, lse2);
     return hipGetLastError();
 }
 
@@ -594,13 +518,11 @@ hipError_t launch_rel_attn_mfma_wide_bwd(const void* qkv, long long ld, const vo
                                          int N, const void* out, long long ldo, const void* u, long long ldu, const void* dout,
                                          long long lddo, const void* du, long long lddu, const float* lse2, float* delta, void* dqkv,
                                          long long lddq, void* dqp, long long lddqp, hipStream_t st) {
-    const long long d = (long long)H * DH;
-    if (!rel_attn_mfma_wide_supported(DH) || ld % 8 || ldqp % 8 || ldo % 8 || ldu % 8 || lddo % 8 || lddu % 8 || lddq % 8 ||
-        lddqp % 8 || ldxt < 4 || ld < 3 * d || lddq < 3 * d || ldqp < d || ldo < d || ldu < d || lddo < d || lddu < d || lddqp < d)
+    if (!rel_attn_mfma_wide_supported(DH) || !rel_args_ok(true, 8, H, DH, ld, ldqp, ldxt, ldo, ldu, lddo, lddu, lddq, lddqp))
         return hipErrorInvalidValue;
     if (N == 0 || B == 0) return hipSuccess;
-    static const hipError_t once_dq = rx_allow_lds(&rel_attn_mfma_wide_bwd_dq_kernel, RX_LDS_DQ);
-    static const hipError_t once_kv = rx_allow_lds(&rel_attn_mfma_wide_bwd_dkv_kernel, RX_LDS_KV);
+    static const hipError_t once_dq = rel_allow_lds(&rel_attn_mfma_wide_bwd_dq_kernel, RX_LDS_DQ);
+    static const hipError_t once_kv = rel_allow_lds(&rel_attn_mfma_wide_bwd_dkv_kernel, RX_LDS_KV);
     if (once_dq != hipSuccess) return once_dq;
     if (once_kv != hipSuccess) return once_kv;
     const __bf16* qkv_ = static_cast<const __bf16*>(qkv);
@@ -608,10 +530,10 @@ hipError_t launch_rel_attn_mfma_wide_bwd(const void* qkv, long long ld, const vo
     const __bf16* dout_ = static_cast<const __bf16*>(dout);
     const __bf16* du_ = static_cast<const __bf16*>(du);
     const long long NH = (long long)N * H;
-    hipLaunchKernelGGL(rel_attn_mfma_wide_delta_kernel, dim3((unsigned)((NH + 255) / 256)), dim3(256), 0, st,
+    hipLaunchKernelGGL(rel_attn_mfma_delta_kernel<RX_DH>, dim3((unsigned)((NH + 255) / 256)), dim3(256), 0, st,
                        static_cast<const __bf16*>(out), ldo, static_cast<const __bf16*>(u), ldu, dout_, lddo, du_, lddu, H, NH, delta);
     const dim3 grid((unsigned)(REL_TILE / RX_ROWS) * (unsigned)(N / REL_TILE + B), (unsigned)((H + RX_G - 1) / RX_G)), block(RX_NT);
-    const float scale = 1.0f / sqrtf((float)DH);
+    const float scale = rel_scale(DH);
     hipLaunchKernelGGL(rel_attn_mfma_wide_bwd_dq_kernel, grid, block, RX_LDS_DQ, st, qkv_, ld, qp_, ldqp, xt, ldxt, freq, H, ptr,
                        tile_ptr, B, scale, dout_, lddo, du_, lddu, lse2, delta, static_cast<__bf16*>(dqkv), lddq,
                        static_cast<__bf16*>(dqp), lddqp);

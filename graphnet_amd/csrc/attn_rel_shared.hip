@@ -43,21 +43,6 @@ constexpr int RS_HF = 16;                          // frequencies
 constexpr int RS_SROW = RS_DH * REL_TILE;          // floats of s_ij per block row: [8 chunks][64 lanes][4]
 constexpr int RS_W = 8;                            // heads per workgroup (waves), all three kernels
 
-// frequencies in revolutions per unit, hi + lo, wave-uniform (the arithmetic of attn_rel.hip's rel_freq_table)
-__device__ __forceinline__ void rs_freq_table(const float* __restrict__ freq, int lane, float (&ghi)[RS_HF], float (&glo)[RS_HF]) {
-    float hi_l = 0.0f, lo_l = 0.0f;
-    if (lane < RS_HF) {
-        const double g = (double)freq[lane] * 0.15915494309189534561;
-        hi_l = (float)g;
-        lo_l = (float)(g - (double)hi_l);
-    }
-#pragma unroll
-    for (int k = 0; k < RS_HF; ++k) {
-        ghi[k] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, hi_l), k));
-        glo[k] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, lo_l), k));
-    }
-}
-
 // s_ij = [sin | cos] of pair argument a -> this lane's 8 chunks of the block row at srow
 __device__ __forceinline__ void rs_produce(float* __restrict__ srow, float a, const float (&ghi)[RS_HF], const float (&glo)[RS_HF],
                                            int lane) {
@@ -68,14 +53,6 @@ __device__ __forceinline__ void rs_produce(float* __restrict__ srow, float a, co
         for (int i = 0; i < 4; ++i) rel_sincos(a, ghi[4 * j + i], glo[4 * j + i], sn[i], cs[i]);
         *reinterpret_cast<float4*>(srow + (j * REL_TILE + lane) * 4) = make_float4(sn[0], sn[1], sn[2], sn[3]);
         *reinterpret_cast<float4*>(srow + ((RS_HF / 4 + j) * REL_TILE + lane) * 4) = make_float4(cs[0], cs[1], cs[2], cs[3]);
-    }
-}
-
-__device__ __forceinline__ void rs_read(float (&sc)[RS_DH], const float* __restrict__ srow, int lane) {
-#pragma unroll
-    for (int j = 0; j < RS_DH / 4; ++j) {
-        const float4 v = *reinterpret_cast<const float4*>(srow + (j * REL_TILE + lane) * 4);
-        sc[4 * j] = v.x; sc[4 * j + 1] = v.y; sc[4 * j + 2] = v.z; sc[4 * j + 3] = v.w;
     }
 }
 
@@ -94,23 +71,11 @@ __device__ __forceinline__ void rs_stage(float* __restrict__ dst, const float* _
     }
 }
 
-__device__ __forceinline__ void rs_load_row(float (&dst)[RS_DH], const float* __restrict__ p, float mul) {
-#pragma unroll
-    for (int d4 = 0; d4 < RS_DH / 4; ++d4) {
-        const float4 v = *reinterpret_cast<const float4*>(p + 4 * d4);
-        dst[4 * d4] = v.x * mul; dst[4 * d4 + 1] = v.y * mul; dst[4 * d4 + 2] = v.z * mul; dst[4 * d4 + 3] = v.w * mul;
-    }
-}
-
 // Tile -> event and rows (the plan of gn_attention_plan), wave -> head.  `hc` is the head whose rows an idle wave loads.
 #define RS_PROLOGUE(ROW0, ROWI)                                                                                 \
     const int tile = blockIdx.x, tid = threadIdx.x, lane = tid & 63;                                            \
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);                                                  \
-    if (tile >= tile_ptr[B]) return;                          /* blockIdx.x alone: the whole workgroup leaves */ \
-    const int es = rel_event_of_tile(tile_ptr, B, tile);                                                        \
-    const int e = tile_ptr[B + 1 + es];                                                                         \
-    const int kbeg = ptr[e], kend = ptr[e + 1];                                                                 \
-    const int ROW0 = kbeg + (tile - tile_ptr[es]) * REL_TILE;                                                   \
+    REL_EVENT_PROLOGUE(ROW0)                                                                                    \
     const int E = H * RS_DH;                                                                                    \
     const int ROWI = ROW0 + lane;                                                                               \
     const bool valid = ROWI < kend;                                                                             \
@@ -132,11 +97,11 @@ __global__ __launch_bounds__(64 * W) void rel_attn_shared_fwd_kernel(
     float* const Vs = Ks + W * W * RS_DH;
     RS_PROLOGUE(q0, qi)
     float ghi[RS_HF], glo[RS_HF];
-    rs_freq_table(freq, lane, ghi, glo);
+    rel_freq_table<RS_HF>(freq, 0, lane, ghi, glo);
     const float4 xi = rel_load_xt(xt, ldxt, myrow);
     float q[RS_DH], qq[RS_DH], o[RS_DH], uu[RS_DH];
-    rs_load_row(q, qkv + (long long)myrow * ld + hc * RS_DH, scale2);
-    rs_load_row(qq, qp + (long long)myrow * ldqp + hc * RS_DH, REL_LOG2E);
+    rel_load_row(q, qkv + (long long)myrow * ld + hc * RS_DH, scale2);
+    rel_load_row(qq, qp + (long long)myrow * ldqp + hc * RS_DH, REL_LOG2E);
 #pragma unroll
     for (int d = 0; d < RS_DH; ++d) { o[d] = 0.0f; uu[d] = 0.0f; }
     float m = -INFINITY, l = 0.0f;
@@ -153,7 +118,7 @@ __global__ __launch_bounds__(64 * W) void rel_attn_shared_fwd_kernel(
             const int nk = min(W, kend - kb);
             for (int c = 0; c < nk; ++c) {
                 float sc[RS_DH];
-                rs_read(sc, Ss + c * RS_SROW, lane);
+                rel_read<RS_DH, REL_TILE>(sc, Ss + c * RS_SROW, lane);
                 float acc = 0.0f;
 #pragma unroll
                 for (int k = 0; k < RS_HF; ++k) {
@@ -219,23 +184,23 @@ __global__ __launch_bounds__(64 * W) void rel_attn_shared_bwd_dq_kernel(
     float* const Vs = Ks + W * W * RS_DH;
     RS_PROLOGUE(q0, qi)
     float ghi[RS_HF], glo[RS_HF];
-    rs_freq_table(freq, lane, ghi, glo);
+    rel_freq_table<RS_HF>(freq, 0, lane, ghi, glo);
     const float4 xi = rel_load_xt(xt, ldxt, myrow);
     const float scale2 = scale * REL_LOG2E;
     float q[RS_DH], qq[RS_DH], go[RS_DH], gu[RS_DH], dq[RS_DH], dqq[RS_DH];
-    rs_load_row(q, qkv + (long long)myrow * ld + hc * RS_DH, scale2);
-    rs_load_row(qq, qp + (long long)myrow * ldqp + hc * RS_DH, REL_LOG2E);
-    rs_load_row(go, dout + (long long)myrow * lddo + hc * RS_DH, 1.0f);
-    rs_load_row(gu, du + (long long)myrow * lddu + hc * RS_DH, 1.0f);
+    rel_load_row(q, qkv + (long long)myrow * ld + hc * RS_DH, scale2);
+    rel_load_row(qq, qp + (long long)myrow * ldqp + hc * RS_DH, REL_LOG2E);
+    rel_load_row(go, dout + (long long)myrow * lddo + hc * RS_DH, 1.0f);
+    rel_load_row(gu, du + (long long)myrow * lddu + hc * RS_DH, 1.0f);
     float dl = 0.0f;
     {
         // delta = dU . U + dO . O, summed in the order in which dA = dU . s + dO . v is summed per key below: with a single
         // key (U = s, O = v bit for bit) dA - delta is then exactly 0, as the softmax of one score has no gradient
         float t[RS_DH];
-        rs_load_row(t, u + (long long)myrow * ldu + hc * RS_DH, 1.0f);
+        rel_load_row(t, u + (long long)myrow * ldu + hc * RS_DH, 1.0f);
 #pragma unroll
         for (int k = 0; k < RS_HF; ++k) { dl = fmaf(gu[k], t[k], dl); dl = fmaf(gu[RS_HF + k], t[RS_HF + k], dl); }
-        rs_load_row(t, out + (long long)myrow * ldo + hc * RS_DH, 1.0f);
+        rel_load_row(t, out + (long long)myrow * ldo + hc * RS_DH, 1.0f);
 #pragma unroll
         for (int d = 0; d < RS_DH; ++d) dl = fmaf(go[d], t[d], dl);
     }
@@ -332,12 +297,12 @@ __global__ __launch_bounds__(64 * W) void rel_attn_shared_bwd_dkv_kernel(
     float* const Ds = Ls + W * W;
     RS_PROLOGUE(k0, kj)
     float ghi[RS_HF], glo[RS_HF];
-    rs_freq_table(freq, lane, ghi, glo);
+    rel_freq_table<RS_HF>(freq, 0, lane, ghi, glo);
     const float4 xj = rel_load_xt(xt, ldxt, myrow);
     const float scale2 = scale * REL_LOG2E;
     float k[RS_DH], v[RS_DH], dk[RS_DH], dv[RS_DH];
-    rs_load_row(k, qkv + (long long)myrow * ld + E + hc * RS_DH, scale2);
-    rs_load_row(v, qkv + (long long)myrow * ld + 2 * E + hc * RS_DH, 1.0f);
+    rel_load_row(k, qkv + (long long)myrow * ld + E + hc * RS_DH, scale2);
+    rel_load_row(v, qkv + (long long)myrow * ld + 2 * E + hc * RS_DH, 1.0f);
 #pragma unroll
     for (int d = 0; d < RS_DH; ++d) { dk[d] = 0.0f; dv[d] = 0.0f; }
     float4 xq = rel_load_xt(xt, ldxt, min(kbeg + wave, kend - 1));
@@ -360,7 +325,7 @@ __global__ __launch_bounds__(64 * W) void rel_attn_shared_bwd_dkv_kernel(
             const int nq = min(W, kend - qb);
             for (int c = 0; c < nq; ++c) {
                 float sc[RS_DH];
-                rs_read(sc, Ss + c * RS_SROW, lane);
+                rel_read<RS_DH, REL_TILE>(sc, Ss + c * RS_SROW, lane);
                 const float* qr = Qs + (c * W + wave) * RS_DH;
                 const float* pr = Ps + (c * W + wave) * RS_DH;
                 const float* gr = Gs + (c * W + wave) * RS_DH;
@@ -413,48 +378,39 @@ constexpr int RS_LDS_QK = RS_W * (RS_SROW + 2 * RS_W * RS_DH) * 4;              
 constexpr int RS_LDS_KV = RS_W * (RS_SROW + 4 * RS_W * RS_DH + 2 * RS_W) * 4;            // dK / dV: s_ij, q, q', dO, dU, lse2, delta
 static_assert(RS_LDS_KV <= 160 * 1024, "one workgroup's LDS");
 
-// more than 64 KB of dynamic LDS has to be asked for once per kernel
-template <typename K>
-static hipError_t rs_allow_lds(K kernel, int bytes) {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-}
-
-hipError_t launch_rel_attn_shared_fwd(const float* qkv, long long ld, const float* qp, long long ldqp, const float* xt,
+hipError_t launch_rel_attn_shared_fwd(const void* qkv, long long ld, const void* qp, long long ldqp, const float* xt,
                                       long long ldxt, const float* freq, int H, int DH, const int* ptr, const int* tile_ptr, int B,
-                                      int N, float* out, long long ldo, float* u, long long ldu, float* lse2, hipStream_t st) {
-    if (!rel_attn_shared_supported(DH) || ld % 4 || ldqp % 4 || ldo % 4 || ldu % 4 || ldxt < 4 || ld < 3ll * H * DH ||
-        ldqp < (long long)H * DH || ldo < (long long)H * DH || ldu < (long long)H * DH)
-        return hipErrorInvalidValue;
+                                      int N, void* out, long long ldo, void* u, long long ldu, float* lse2, hipStream_t st) {
+    if (!rel_attn_shared_supported(DH) || !rel_args_ok(false, 4, H, DH, ld, ldqp, ldxt, ldo, ldu)) return hipErrorInvalidValue;
     if (N == 0 || B == 0) return hipSuccess;
-    static const hipError_t once = rs_allow_lds(&rel_attn_shared_fwd_kernel<RS_W>, RS_LDS_QK);
+    static const hipError_t once = rel_allow_lds(&rel_attn_shared_fwd_kernel<RS_W>, RS_LDS_QK);
     if (once != hipSuccess) return once;
     const dim3 grid((unsigned)(N / REL_TILE + B), (unsigned)((H + RS_W - 1) / RS_W)), block(64 * RS_W);
-    const float scale2 = REL_LOG2E / sqrtf((float)DH);
-    hipLaunchKernelGGL((rel_attn_shared_fwd_kernel<RS_W>), grid, block, RS_LDS_QK, st, qkv, ld, qp, ldqp, xt, ldxt, freq, H, ptr,
-                       tile_ptr, B, scale2, out, ldo, u, ldu, lse2);
+    hipLaunchKernelGGL((rel_attn_shared_fwd_kernel<RS_W>), grid, block, RS_LDS_QK, st, (const float*)qkv, ld, (const float*)qp, ldqp,
+                       xt, ldxt, freq, H, ptr, tile_ptr, B, rel_scale2(DH), (float*)out, ldo, (float*)u, ldu, lse2);
     return hipGetLastError();
 }
 
-hipError_t launch_rel_attn_shared_bwd(const float* qkv, long long ld, const float* qp, long long ldqp, const float* xt,
+hipError_t launch_rel_attn_shared_bwd(const void* qkv, long long ld, const void* qp, long long ldqp, const float* xt,
                                       long long ldxt, const float* freq, int H, int DH, const int* ptr, const int* tile_ptr, int B,
-                                      int N, const float* out, long long ldo, const float* u, long long ldu, const float* dout,
-                                      long long lddo, const float* du, long long lddu, const float* lse2, float* delta,
-                                      float* dqkv, long long lddq, float* dqp, long long lddqp, hipStream_t st) {
-    const long long d = (long long)H * DH;
-    if (!rel_attn_shared_supported(DH) || ld % 4 || ldqp % 4 || ldo % 4 || ldu % 4 || lddo % 4 || lddu % 4 || lddq % 4 ||
-        lddqp % 4 || ldxt < 4 || ld < 3 * d || lddq < 3 * d || ldqp < d || ldo < d || ldu < d || lddo < d || lddu < d || lddqp < d)
+                                      int N, const void* out, long long ldo, const void* u, long long ldu, const void* dout,
+                                      long long lddo, const void* du, long long lddu, const float* lse2, float* delta,
+                                      void* dqkv, long long lddq, void* dqp, long long lddqp, hipStream_t st) {
+    if (!rel_attn_shared_supported(DH) || !rel_args_ok(true, 4, H, DH, ld, ldqp, ldxt, ldo, ldu, lddo, lddu, lddq, lddqp))
         return hipErrorInvalidValue;
     if (N == 0 || B == 0) return hipSuccess;
-    static const hipError_t once_dq = rs_allow_lds(&rel_attn_shared_bwd_dq_kernel<RS_W>, RS_LDS_QK);
-    static const hipError_t once_kv = rs_allow_lds(&rel_attn_shared_bwd_dkv_kernel<RS_W>, RS_LDS_KV);
+    static const hipError_t once_dq = rel_allow_lds(&rel_attn_shared_bwd_dq_kernel<RS_W>, RS_LDS_QK);
+    static const hipError_t once_kv = rel_allow_lds(&rel_attn_shared_bwd_dkv_kernel<RS_W>, RS_LDS_KV);
     if (once_dq != hipSuccess) return once_dq;
     if (once_kv != hipSuccess) return once_kv;
     const dim3 grid((unsigned)(N / REL_TILE + B), (unsigned)((H + RS_W - 1) / RS_W)), block(64 * RS_W);
-    const float scale = 1.0f / sqrtf((float)DH);
-    hipLaunchKernelGGL((rel_attn_shared_bwd_dq_kernel<RS_W>), grid, block, RS_LDS_QK, st, qkv, ld, qp, ldqp, xt, ldxt, freq, H, ptr,
-                       tile_ptr, B, scale, out, ldo, u, ldu, dout, lddo, du, lddu, lse2, delta, dqkv, lddq, dqp, lddqp);
-    hipLaunchKernelGGL((rel_attn_shared_bwd_dkv_kernel<RS_W>), grid, block, RS_LDS_KV, st, qkv, ld, qp, ldqp, xt, ldxt, freq, H,
-                       ptr, tile_ptr, B, scale, dout, lddo, du, lddu, lse2, delta, dqkv, lddq);
+    const float scale = rel_scale(DH);
+    hipLaunchKernelGGL((rel_attn_shared_bwd_dq_kernel<RS_W>), grid, block, RS_LDS_QK, st, (const float*)qkv, ld, (const float*)qp,
+                       ldqp, xt, ldxt, freq, H, ptr, tile_ptr, B, scale, (const float*)out, ldo, (const float*)u, ldu,
+                       (const float*)dout, lddo, (const float*)du, lddu, lse2, delta, (float*)dqkv, lddq, (float*)dqp, lddqp);
+    hipLaunchKernelGGL((rel_attn_shared_bwd_dkv_kernel<RS_W>), grid, block, RS_LDS_KV, st, (const float*)qkv, ld, (const float*)qp,
+                       ldqp, xt, ldxt, freq, H, ptr, tile_ptr, B, scale, (const float*)dout, lddo, (const float*)du, lddu, lse2,
+                       delta, (float*)dqkv, lddq);
     return hipGetLastError();
 }
 

@@ -33,14 +33,8 @@ constexpr int RW_HF = 16;                 // frequencies per lane
 constexpr int RW_THREADS = 128;
 constexpr int RW_QT = 32;                 // queries per LDS stage of the dK / dV pass
 
-// x of this lane + x of its partner lane l ^ 32, as half0 + half1 on both
-__device__ __forceinline__ float rw_pair_sum(float x) {
-    const unsigned b = __builtin_bit_cast(unsigned, x);
-    const auto r = __builtin_amdgcn_permlane32_swap(b, b, false, false);     // {x of lane l & 31, x of lane 32 + (l & 31)}
-    return __builtin_bit_cast(float, (unsigned)r[0]) + __builtin_bit_cast(float, (unsigned)r[1]);
-}
-
-// hi + lo of f_k / 2 pi for the 16 frequencies of half h (the double arithmetic of rel_freq_table)
+// hi + lo of f_k / 2 pi for the 16 frequencies of half h (the double arithmetic of rel_freq_table; the half differs between
+// the lanes of a wave, so every lane forms its own table)
 __device__ __forceinline__ void rw_freq_table(const float* __restrict__ freq, int half, float (&ghi)[RW_HF], float (&glo)[RW_HF]) {
 #pragma unroll
     for (int k = 0; k < RW_HF; ++k) {
@@ -50,43 +44,7 @@ __device__ __forceinline__ void rw_freq_table(const float* __restrict__ freq, in
     }
 }
 
-// 32 contiguous floats at p (16-byte aligned), times mul
-__device__ __forceinline__ void rw_load_row(float (&dst)[RW_HALF], const float* __restrict__ p, float mul) {
-#pragma unroll
-    for (int d4 = 0; d4 < RW_HALF / 4; ++d4) {
-        const float4 v = *reinterpret_cast<const float4*>(p + 4 * d4);
-        dst[4 * d4] = v.x * mul; dst[4 * d4 + 1] = v.y * mul; dst[4 * d4 + 2] = v.z * mul; dst[4 * d4 + 3] = v.w * mul;
-    }
-}
-
-// the embedding half at p = row + head * 64 + 16 h: dst[k] = sine column p[k], dst[16 + k] = cosine column p[32 + k]
-__device__ __forceinline__ void rw_load_emb(float (&dst)[RW_HALF], const float* __restrict__ p, float mul) {
-#pragma unroll
-    for (int part = 0; part < 2; ++part)
-#pragma unroll
-        for (int d4 = 0; d4 < RW_HF / 4; ++d4) {
-            const float4 v = *reinterpret_cast<const float4*>(p + 32 * part + 4 * d4);
-            float* d = dst + RW_HF * part + 4 * d4;
-            d[0] = v.x * mul; d[1] = v.y * mul; d[2] = v.z * mul; d[3] = v.w * mul;
-        }
-}
-
-__device__ __forceinline__ void rw_store_row(float* __restrict__ p, const float (&src)[RW_HALF], float mul) {
-#pragma unroll
-    for (int d4 = 0; d4 < RW_HALF / 4; ++d4)
-        *reinterpret_cast<float4*>(p + 4 * d4) =
-            make_float4(src[4 * d4] * mul, src[4 * d4 + 1] * mul, src[4 * d4 + 2] * mul, src[4 * d4 + 3] * mul);
-}
-
-__device__ __forceinline__ void rw_store_emb(float* __restrict__ p, const float (&src)[RW_HALF], float mul) {
-#pragma unroll
-    for (int part = 0; part < 2; ++part)
-#pragma unroll
-        for (int d4 = 0; d4 < RW_HF / 4; ++d4) {
-            const float* s = src + RW_HF * part + 4 * d4;
-            *reinterpret_cast<float4*>(p + 32 * part + 4 * d4) = make_float4(s[0] * mul, s[1] * mul, s[2] * mul, s[3] * mul);
-        }
-}
+static_assert(RW_HALF == 32 && RW_HF == 16, "rel_load_emb / rel_store_emb: 16 sine and 16 cosine columns per lane, 32 apart");
 
 // thread -> row of the tile (wave w, lane l: 32 w + (l & 31)); the half is (lane >> 5) & 1
 #define RW_PROLOGUE(ROW0, ROWI)                                                                                 \
@@ -109,8 +67,8 @@ __global__ __launch_bounds__(RW_THREADS) void rel_attn_wide_fwd_kernel(
     rw_freq_table(freq, half, ghi, glo);
     const float4 xi = rel_load_xt(xt, ldxt, myrow);
     float q[RW_HALF], qq[RW_HALF], o[RW_HALF], uu[RW_HALF];
-    rw_load_row(q, qkv + (long long)myrow * ld + crow, scale2);
-    rw_load_emb(qq, qp + (long long)myrow * ldqp + cemb, REL_LOG2E);
+    rel_load_row(q, qkv + (long long)myrow * ld + crow, scale2);
+    rel_load_emb(qq, qp + (long long)myrow * ldqp + cemb, REL_LOG2E);
 #pragma unroll
     for (int d = 0; d < RW_HALF; ++d) { o[d] = 0.0f; uu[d] = 0.0f; }
     float m = -INFINITY, l = 0.0f;
@@ -138,7 +96,7 @@ __global__ __launch_bounds__(RW_THREADS) void rel_attn_wide_fwd_kernel(
                 acc = fmaf(q[4 * d4], kk.x, acc); acc = fmaf(q[4 * d4 + 1], kk.y, acc);
                 acc = fmaf(q[4 * d4 + 2], kk.z, acc); acc = fmaf(q[4 * d4 + 3], kk.w, acc);
             }
-            acc = rw_pair_sum(acc);                         // the score, the same bits on both halves
+            acc = rel_pair_sum(acc);                         // the score, the same bits on both halves
             if (acc > m) {                                  // a new maximum: rescale what has been summed so far
                 const float corr = exp2f(m - acc);
                 l *= corr;
@@ -161,8 +119,8 @@ __global__ __launch_bounds__(RW_THREADS) void rel_attn_wide_fwd_kernel(
     }
     if (valid) {
         const float inv = 1.0f / l;
-        rw_store_row(out + (long long)qi * ldo + crow, o, inv);
-        rw_store_emb(u + (long long)qi * ldu + cemb, uu, inv);
+        rel_store_row(out + (long long)qi * ldo + crow, o, inv);
+        rel_store_emb(u + (long long)qi * ldu + cemb, uu, inv);
         if (half == 0) lse2[(long long)qi * H + head] = m + log2f(l);
     }
 }
@@ -184,22 +142,22 @@ __global__ __launch_bounds__(RW_THREADS) void rel_attn_wide_bwd_dq_kernel(
     const float4 xi = rel_load_xt(xt, ldxt, myrow);
     const float scale2 = scale * REL_LOG2E;
     float q[RW_HALF], qq[RW_HALF], go[RW_HALF], gu[RW_HALF], dq[RW_HALF], dqq[RW_HALF];
-    rw_load_row(q, qkv + (long long)myrow * ld + crow, scale2);
-    rw_load_emb(qq, qp + (long long)myrow * ldqp + cemb, REL_LOG2E);
-    rw_load_row(go, dout + (long long)myrow * lddo + crow, 1.0f);
-    rw_load_emb(gu, du + (long long)myrow * lddu + cemb, 1.0f);
+    rel_load_row(q, qkv + (long long)myrow * ld + crow, scale2);
+    rel_load_emb(qq, qp + (long long)myrow * ldqp + cemb, REL_LOG2E);
+    rel_load_row(go, dout + (long long)myrow * lddo + crow, 1.0f);
+    rel_load_emb(gu, du + (long long)myrow * lddu + cemb, 1.0f);
     float dl = 0.0f;
     {
         // delta = dU . U + dO . O, per half in the order in which dA = dU . s + dO . v is summed per key below, then the same
         // half0 + half1: with a single key (U = s, O = v bit for bit) dA - delta is exactly 0
         float t[RW_HALF];
-        rw_load_emb(t, u + (long long)myrow * ldu + cemb, 1.0f);
+        rel_load_emb(t, u + (long long)myrow * ldu + cemb, 1.0f);
 #pragma unroll
         for (int k = 0; k < RW_HF; ++k) { dl = fmaf(gu[k], t[k], dl); dl = fmaf(gu[RW_HF + k], t[RW_HF + k], dl); }
-        rw_load_row(t, out + (long long)myrow * ldo + crow, 1.0f);
+        rel_load_row(t, out + (long long)myrow * ldo + crow, 1.0f);
 #pragma unroll
         for (int d = 0; d < RW_HALF; ++d) dl = fmaf(go[d], t[d], dl);
-        dl = rw_pair_sum(dl);
+        dl = rel_pair_sum(dl);
     }
 #pragma unroll
     for (int d = 0; d < RW_HALF; ++d) { dq[d] = 0.0f; dqq[d] = 0.0f; }
@@ -232,8 +190,8 @@ __global__ __launch_bounds__(RW_THREADS) void rel_attn_wide_bwd_dq_kernel(
                 dp = fmaf(go[4 * d4], vv.x, dp); dp = fmaf(go[4 * d4 + 1], vv.y, dp);
                 dp = fmaf(go[4 * d4 + 2], vv.z, dp); dp = fmaf(go[4 * d4 + 3], vv.w, dp);
             }
-            s = rw_pair_sum(s);
-            dp = rw_pair_sum(dp);
+            s = rel_pair_sum(s);
+            dp = rel_pair_sum(dp);
             const float dS = exp2f(s - ls) * (dp - dl);
 #pragma unroll
             for (int d4 = 0; d4 < RW_HALF / 4; ++d4) {
@@ -246,8 +204,8 @@ __global__ __launch_bounds__(RW_THREADS) void rel_attn_wide_bwd_dq_kernel(
         }
     }
     if (valid) {
-        rw_store_row(dqkv + (long long)qi * lddq + crow, dq, scale);
-        rw_store_emb(dqp + (long long)qi * lddqp + cemb, dqq, 1.0f);
+        rel_store_row(dqkv + (long long)qi * lddq + crow, dq, scale);
+        rel_store_emb(dqp + (long long)qi * lddqp + cemb, dqq, 1.0f);
         if (half == 0) delta[(long long)qi * H + head] = dl;
     }
 }
@@ -273,8 +231,8 @@ __global__ __launch_bounds__(RW_THREADS) void rel_attn_wide_bwd_dkv_kernel(
     const float4 xj = rel_load_xt(xt, ldxt, myrow);
     const float scale2 = scale * REL_LOG2E;
     float k[RW_HALF], v[RW_HALF], dk[RW_HALF], dv[RW_HALF];
-    rw_load_row(k, qkv + (long long)myrow * ld + E + crow, scale2);
-    rw_load_row(v, qkv + (long long)myrow * ld + 2 * E + crow, 1.0f);
+    rel_load_row(k, qkv + (long long)myrow * ld + E + crow, scale2);
+    rel_load_row(v, qkv + (long long)myrow * ld + 2 * E + crow, 1.0f);
 #pragma unroll
     for (int d = 0; d < RW_HALF; ++d) { dk[d] = 0.0f; dv[d] = 0.0f; }
     for (int qt = kbeg; qt < kend; qt += RW_QT) {
@@ -315,8 +273,8 @@ __global__ __launch_bounds__(RW_THREADS) void rel_attn_wide_bwd_dkv_kernel(
                 dp = fmaf(v[4 * d4], gg.x, dp); dp = fmaf(v[4 * d4 + 1], gg.y, dp);
                 dp = fmaf(v[4 * d4 + 2], gg.z, dp); dp = fmaf(v[4 * d4 + 3], gg.w, dp);
             }
-            s = rw_pair_sum(s);
-            dp = rw_pair_sum(dp);
+            s = rel_pair_sum(s);
+            dp = rel_pair_sum(dp);
             const float p = exp2f(s - Ls[c]);
             const float dS = p * (dp - Ds[c]);
 #pragma unroll
@@ -331,44 +289,41 @@ __global__ __launch_bounds__(RW_THREADS) void rel_attn_wide_bwd_dkv_kernel(
         }
     }
     if (valid) {
-        rw_store_row(dqkv + (long long)kj * lddq + E + crow, dk, scale);
-        rw_store_row(dqkv + (long long)kj * lddq + 2 * E + crow, dv, 1.0f);
+        rel_store_row(dqkv + (long long)kj * lddq + E + crow, dk, scale);
+        rel_store_row(dqkv + (long long)kj * lddq + 2 * E + crow, dv, 1.0f);
     }
 }
 #undef RW_PROLOGUE
 
 bool rel_attn_wide_supported(int DH) { return DH == RW_DH; }
 
-hipError_t launch_rel_attn_wide_fwd(const float* qkv, long long ld, const float* qp, long long ldqp, const float* xt,
+hipError_t launch_rel_attn_wide_fwd(const void* qkv, long long ld, const void* qp, long long ldqp, const float* xt,
                                     long long ldxt, const float* freq, int H, int DH, const int* ptr, const int* tile_ptr, int B,
-                                    int N, float* out, long long ldo, float* u, long long ldu, float* lse2, hipStream_t st) {
-    if (!rel_attn_wide_supported(DH) || ld % 4 || ldqp % 4 || ldo % 4 || ldu % 4 || ldxt < 4 || ld < 3ll * H * DH ||
-        ldqp < (long long)H * DH || ldo < (long long)H * DH || ldu < (long long)H * DH)
-        return hipErrorInvalidValue;
+                                    int N, void* out, long long ldo, void* u, long long ldu, float* lse2, hipStream_t st) {
+    if (!rel_attn_wide_supported(DH) || !rel_args_ok(false, 4, H, DH, ld, ldqp, ldxt, ldo, ldu)) return hipErrorInvalidValue;
     if (N == 0 || B == 0) return hipSuccess;
     const dim3 grid((unsigned)(N / REL_TILE + B), (unsigned)H), block(RW_THREADS);
-    const float scale2 = REL_LOG2E / sqrtf((float)DH);
-    hipLaunchKernelGGL(rel_attn_wide_fwd_kernel, grid, block, 0, st, qkv, ld, qp, ldqp, xt, ldxt, freq, H, ptr, tile_ptr, B,
-                       scale2, out, ldo, u, ldu, lse2);
+    hipLaunchKernelGGL(rel_attn_wide_fwd_kernel, grid, block, 0, st, (const float*)qkv, ld, (const float*)qp, ldqp, xt, ldxt, freq,
+                       H, ptr, tile_ptr, B, rel_scale2(DH), (float*)out, ldo, (float*)u, ldu, lse2);
     return hipGetLastError();
 }
 
-hipError_t launch_rel_attn_wide_bwd(const float* qkv, long long ld, const float* qp, long long ldqp, const float* xt,
+hipError_t launch_rel_attn_wide_bwd(const void* qkv, long long ld, const void* qp, long long ldqp, const float* xt,
                                     long long ldxt, const float* freq, int H, int DH, const int* ptr, const int* tile_ptr, int B,
-                                    int N, const float* out, long long ldo, const float* u, long long ldu, const float* dout,
-                                    long long lddo, const float* du, long long lddu, const float* lse2, float* delta,
-                                    float* dqkv, long long lddq, float* dqp, long long lddqp, hipStream_t st) {
-    const long long d = (long long)H * DH;
-    if (!rel_attn_wide_supported(DH) || ld % 4 || ldqp % 4 || ldo % 4 || ldu % 4 || lddo % 4 || lddu % 4 || lddq % 4 ||
-        lddqp % 4 || ldxt < 4 || ld < 3 * d || lddq < 3 * d || ldqp < d || ldo < d || ldu < d || lddo < d || lddu < d || lddqp < d)
+                                    int N, const void* out, long long ldo, const void* u, long long ldu, const void* dout,
+                                    long long lddo, const void* du, long long lddu, const float* lse2, float* delta,
+                                    void* dqkv, long long lddq, void* dqp, long long lddqp, hipStream_t st) {
+    if (!rel_attn_wide_supported(DH) || !rel_args_ok(true, 4, H, DH, ld, ldqp, ldxt, ldo, ldu, lddo, lddu, lddq, lddqp))
         return hipErrorInvalidValue;
     if (N == 0 || B == 0) return hipSuccess;
     const dim3 grid((unsigned)(N / REL_TILE + B), (unsigned)H), block(RW_THREADS);
-    const float scale = 1.0f / sqrtf((float)DH);
-    hipLaunchKernelGGL(rel_attn_wide_bwd_dq_kernel, grid, block, 0, st, qkv, ld, qp, ldqp, xt, ldxt, freq, H, ptr, tile_ptr, B,
-                       scale, out, ldo, u, ldu, dout, lddo, du, lddu, lse2, delta, dqkv, lddq, dqp, lddqp);
-    hipLaunchKernelGGL(rel_attn_wide_bwd_dkv_kernel, grid, block, 0, st, qkv, ld, qp, ldqp, xt, ldxt, freq, H, ptr, tile_ptr, B,
-                       scale, dout, lddo, du, lddu, lse2, delta, dqkv, lddq);
+    const float scale = rel_scale(DH);
+    hipLaunchKernelGGL(rel_attn_wide_bwd_dq_kernel, grid, block, 0, st, (const float*)qkv, ld, (const float*)qp, ldqp, xt, ldxt,
+                       freq, H, ptr, tile_ptr, B, scale, (const float*)out, ldo, (const float*)u, ldu, (const float*)dout, lddo,
+                       (const float*)du, lddu, lse2, delta, (float*)dqkv, lddq, (float*)dqp, lddqp);
+    hipLaunchKernelGGL(rel_attn_wide_bwd_dkv_kernel, grid, block, 0, st, (const float*)qkv, ld, (const float*)qp, ldqp, xt, ldxt,
+                       freq, H, ptr, tile_ptr, B, scale, (const float*)dout, lddo, (const float*)du, lddu, lse2, delta,
+                       (float*)dqkv, lddq);
     return hipGetLastError();
 }
 

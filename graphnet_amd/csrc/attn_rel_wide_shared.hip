@@ -50,13 +50,6 @@ constexpr int WS_UNITS = 2 * REL_TILE;             // (row, half) units of a til
 constexpr int WS_SROW = WS_HALF * WS_UNITS;        // floats of s_ij per block row: [8 chunks][128 units][4]
 constexpr int WS_G = 4;                            // heads per workgroup (wave pairs), all three kernels
 
-// x of this lane + x of its partner lane l ^ 32, as half0 + half1 on both (attn_rel_wide.hip's rw_pair_sum)
-__device__ __forceinline__ float ws_pair_sum(float x) {
-    const unsigned b = __builtin_bit_cast(unsigned, x);
-    const auto r = __builtin_amdgcn_permlane32_swap(b, b, false, false);
-    return __builtin_bit_cast(float, (unsigned)r[0]) + __builtin_bit_cast(float, (unsigned)r[1]);
-}
-
 // hi + lo of f_k / 2 pi (the double arithmetic of rel_freq_table) -> LDS [half][16 hi | 16 lo], by threads 0 .. 31.  The first
 // barrier of the block loop stands between this and the first ws_produce.
 __device__ __forceinline__ void ws_freq_table(float* __restrict__ Fs, const float* __restrict__ freq, int tid) {
@@ -86,14 +79,6 @@ __device__ __forceinline__ void ws_produce(float* __restrict__ srow, float a, co
     }
 }
 
-__device__ __forceinline__ void ws_read(float (&sc)[WS_HALF], const float* __restrict__ srow, int unit) {
-#pragma unroll
-    for (int j = 0; j < WS_HALF / 4; ++j) {
-        const float4 v = *reinterpret_cast<const float4*>(srow + (j * WS_UNITS + unit) * 4);
-        sc[4 * j] = v.x; sc[4 * j + 1] = v.y; sc[4 * j + 2] = v.z; sc[4 * j + 3] = v.w;
-    }
-}
-
 // rows [r0, r0 + G) (clamped to r_last) of the G heads from head0 (clamped to H - 1: a column past the last head would leave
 // the row) at column col0 + head * 64 -> LDS [row][head of the group][64]: G G 16 float4, one per thread t < G G 16.  With
 // 128 G threads and G < 8 a tensor does not need them all; the callers rotate t so that the tensors spread over the waves.
@@ -108,55 +93,13 @@ __device__ __forceinline__ void ws_stage(float* __restrict__ dst, const float* _
     }
 }
 
-// 32 contiguous floats at p (16-byte aligned), times mul
-__device__ __forceinline__ void ws_load_row(float (&dst)[WS_HALF], const float* __restrict__ p, float mul) {
-#pragma unroll
-    for (int d4 = 0; d4 < WS_HALF / 4; ++d4) {
-        const float4 v = *reinterpret_cast<const float4*>(p + 4 * d4);
-        dst[4 * d4] = v.x * mul; dst[4 * d4 + 1] = v.y * mul; dst[4 * d4 + 2] = v.z * mul; dst[4 * d4 + 3] = v.w * mul;
-    }
-}
-
-// the embedding half at p = row + head * 64 + 16 h: dst[k] = sine column p[k], dst[16 + k] = cosine column p[32 + k]
-__device__ __forceinline__ void ws_load_emb(float (&dst)[WS_HALF], const float* __restrict__ p, float mul) {
-#pragma unroll
-    for (int part = 0; part < 2; ++part)
-#pragma unroll
-        for (int d4 = 0; d4 < WS_HF / 4; ++d4) {
-            const float4 v = *reinterpret_cast<const float4*>(p + 32 * part + 4 * d4);
-            float* d = dst + WS_HF * part + 4 * d4;
-            d[0] = v.x * mul; d[1] = v.y * mul; d[2] = v.z * mul; d[3] = v.w * mul;
-        }
-}
-
-__device__ __forceinline__ void ws_store_row(float* __restrict__ p, const float (&src)[WS_HALF], float mul) {
-#pragma unroll
-    for (int d4 = 0; d4 < WS_HALF / 4; ++d4)
-        *reinterpret_cast<float4*>(p + 4 * d4) =
-            make_float4(src[4 * d4] * mul, src[4 * d4 + 1] * mul, src[4 * d4 + 2] * mul, src[4 * d4 + 3] * mul);
-}
-
-__device__ __forceinline__ void ws_store_emb(float* __restrict__ p, const float (&src)[WS_HALF], float mul) {
-#pragma unroll
-    for (int part = 0; part < 2; ++part)
-#pragma unroll
-        for (int d4 = 0; d4 < WS_HF / 4; ++d4) {
-            const float* s = src + WS_HF * part + 4 * d4;
-            *reinterpret_cast<float4*>(p + 32 * part + 4 * d4) = make_float4(s[0] * mul, s[1] * mul, s[2] * mul, s[3] * mul);
-        }
-}
-
 // Tile -> event and rows (the plan of gn_attention_plan), wave -> (head of the group, parity), lane -> (row, half).  `hc` is
 // the head whose rows an idle wave pair loads; `tswap` is the thread index rotated by half a workgroup (ws_stage).
 #define WS_PROLOGUE(ROW0, ROWI)                                                                                 \
     constexpr int NT = 128 * G;                                                                                 \
     const int tile = blockIdx.x, tid = threadIdx.x, lane = tid & 63;                                            \
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);                                                  \
-    if (tile >= tile_ptr[B]) return;                          /* blockIdx.x alone: the whole workgroup leaves */ \
-    const int es = rel_event_of_tile(tile_ptr, B, tile);                                                        \
-    const int e = tile_ptr[B + 1 + es];                                                                         \
-    const int kbeg = ptr[e], kend = ptr[e + 1];                                                                 \
-    const int ROW0 = kbeg + (tile - tile_ptr[es]) * REL_TILE;                                                   \
+    REL_EVENT_PROLOGUE(ROW0)                                                                                    \
     const int E = H * WS_DH;                                                                                    \
     const int g = wave >> 1, half = lane >> 5;                                                                  \
     const int unit = (wave & 1) * 64 + lane;                                                                    \
@@ -188,8 +131,8 @@ __global__ __launch_bounds__(128 * G) void rel_attn_wide_shared_fwd_kernel(
     const float* const ft = Fs + half * 2 * WS_HF;
     const float4 xi = rel_load_xt(xt, ldxt, myrow);
     float q[WS_HALF], qq[WS_HALF], o[WS_HALF], uu[WS_HALF];
-    ws_load_row(q, qkv + (long long)myrow * ld + crow, scale2);
-    ws_load_emb(qq, qp + (long long)myrow * ldqp + cemb, REL_LOG2E);
+    rel_load_row(q, qkv + (long long)myrow * ld + crow, scale2);
+    rel_load_emb(qq, qp + (long long)myrow * ldqp + cemb, REL_LOG2E);
 #pragma unroll
     for (int d = 0; d < WS_HALF; ++d) { o[d] = 0.0f; uu[d] = 0.0f; }
     float m = -INFINITY, l = 0.0f;
@@ -206,7 +149,7 @@ __global__ __launch_bounds__(128 * G) void rel_attn_wide_shared_fwd_kernel(
             const int nk = min(G, kend - kb);
             for (int c = 0; c < nk; ++c) {
                 float sc[WS_HALF];
-                ws_read(sc, Ss + c * WS_SROW, unit);
+                rel_read<WS_HALF, WS_UNITS>(sc, Ss + c * WS_SROW, unit);
                 float acc = 0.0f;
 #pragma unroll
                 for (int k = 0; k < WS_HF; ++k) {
@@ -220,7 +163,7 @@ __global__ __launch_bounds__(128 * G) void rel_attn_wide_shared_fwd_kernel(
                     acc = fmaf(q[4 * d4], kk.x, acc); acc = fmaf(q[4 * d4 + 1], kk.y, acc);
                     acc = fmaf(q[4 * d4 + 2], kk.z, acc); acc = fmaf(q[4 * d4 + 3], kk.w, acc);
                 }
-                acc = ws_pair_sum(acc);                         // the score, the same bits on both halves
+                acc = rel_pair_sum(acc);                         // the score, the same bits on both halves
                 if (acc > m) {                                  // a new maximum: rescale what has been summed so far
                     const float corr = exp2f(m - acc);
                     l *= corr;
@@ -244,8 +187,8 @@ __global__ __launch_bounds__(128 * G) void rel_attn_wide_shared_fwd_kernel(
     }
     if (valid && active) {
         const float inv = 1.0f / l;
-        ws_store_row(out + (long long)qi * ldo + crow, o, inv);
-        ws_store_emb(u + (long long)qi * ldu + cemb, uu, inv);
+        rel_store_row(out + (long long)qi * ldo + crow, o, inv);
+        rel_store_emb(u + (long long)qi * ldu + cemb, uu, inv);
         if (half == 0) lse2[(long long)qi * H + head] = m + log2f(l);
     }
 }
@@ -273,22 +216,22 @@ __global__ __launch_bounds__(128 * G) void rel_attn_wide_shared_bwd_dq_kernel(
     const float4 xi = rel_load_xt(xt, ldxt, myrow);
     const float scale2 = scale * REL_LOG2E;
     float q[WS_HALF], qq[WS_HALF], go[WS_HALF], gu[WS_HALF], dq[WS_HALF], dqq[WS_HALF];
-    ws_load_row(q, qkv + (long long)myrow * ld + crow, scale2);
-    ws_load_emb(qq, qp + (long long)myrow * ldqp + cemb, REL_LOG2E);
-    ws_load_row(go, dout + (long long)myrow * lddo + crow, 1.0f);
-    ws_load_emb(gu, du + (long long)myrow * lddu + cemb, 1.0f);
+    rel_load_row(q, qkv + (long long)myrow * ld + crow, scale2);
+    rel_load_emb(qq, qp + (long long)myrow * ldqp + cemb, REL_LOG2E);
+    rel_load_row(go, dout + (long long)myrow * lddo + crow, 1.0f);
+    rel_load_emb(gu, du + (long long)myrow * lddu + cemb, 1.0f);
     float dl = 0.0f;
     {
         // delta = dU . U + dO . O, per half in the order in which dA = dU . s + dO . v is summed per key below, then the same
         // half0 + half1: with a single key (U = s, O = v bit for bit) dA - delta is exactly 0
         float t[WS_HALF];
-        ws_load_emb(t, u + (long long)myrow * ldu + cemb, 1.0f);
+        rel_load_emb(t, u + (long long)myrow * ldu + cemb, 1.0f);
 #pragma unroll
         for (int k = 0; k < WS_HF; ++k) { dl = fmaf(gu[k], t[k], dl); dl = fmaf(gu[WS_HF + k], t[WS_HF + k], dl); }
-        ws_load_row(t, out + (long long)myrow * ldo + crow, 1.0f);
+        rel_load_row(t, out + (long long)myrow * ldo + crow, 1.0f);
 #pragma unroll
         for (int d = 0; d < WS_HALF; ++d) dl = fmaf(go[d], t[d], dl);
-        dl = ws_pair_sum(dl);
+        dl = rel_pair_sum(dl);
     }
 #pragma unroll
     for (int d = 0; d < WS_HALF; ++d) { dq[d] = 0.0f; dqq[d] = 0.0f; }
@@ -334,8 +277,8 @@ __global__ __launch_bounds__(128 * G) void rel_attn_wide_shared_bwd_dq_kernel(
                     dp = fmaf(go[4 * d4 + 2], vv.z, dp); dp = fmaf(go[4 * d4 + 3], vv.w, dp);
                     __builtin_amdgcn_sched_barrier(0);
                 }
-                s = ws_pair_sum(s);
-                dp = ws_pair_sum(dp);
+                s = rel_pair_sum(s);
+                dp = rel_pair_sum(dp);
                 const float dS = exp2f(s - ls) * (dp - dl);
 #pragma unroll
                 for (int d4 = 0; d4 < WS_HALF / 4; ++d4) {
@@ -355,8 +298,8 @@ __global__ __launch_bounds__(128 * G) void rel_attn_wide_shared_bwd_dq_kernel(
         }
     }
     if (valid && active) {
-        ws_store_row(dqkv + (long long)qi * lddq + crow, dq, scale);
-        ws_store_emb(dqp + (long long)qi * lddqp + cemb, dqq, 1.0f);
+        rel_store_row(dqkv + (long long)qi * lddq + crow, dq, scale);
+        rel_store_emb(dqp + (long long)qi * lddqp + cemb, dqq, 1.0f);
         if (half == 0) delta[(long long)qi * H + head] = dl;
     }
 }
@@ -386,8 +329,8 @@ __global__ __launch_bounds__(128 * G) void rel_attn_wide_shared_bwd_dkv_kernel(
     const float4 xj = rel_load_xt(xt, ldxt, myrow);
     const float scale2 = scale * REL_LOG2E;
     float k[WS_HALF], v[WS_HALF], dk[WS_HALF], dv[WS_HALF];
-    ws_load_row(k, qkv + (long long)myrow * ld + E + crow, scale2);
-    ws_load_row(v, qkv + (long long)myrow * ld + 2 * E + crow, 1.0f);
+    rel_load_row(k, qkv + (long long)myrow * ld + E + crow, scale2);
+    rel_load_row(v, qkv + (long long)myrow * ld + 2 * E + crow, 1.0f);
 #pragma unroll
     for (int d = 0; d < WS_HALF; ++d) { dk[d] = 0.0f; dv[d] = 0.0f; }
     float4 xq = rel_load_xt(xt, ldxt, min(kbeg + g, kend - 1));
@@ -410,7 +353,7 @@ __global__ __launch_bounds__(128 * G) void rel_attn_wide_shared_bwd_dkv_kernel(
             const int nq = min(G, kend - qb);
             for (int c = 0; c < nq; ++c) {
                 float sc[WS_HALF];
-                ws_read(sc, Ss + c * WS_SROW, unit);
+                rel_read<WS_HALF, WS_UNITS>(sc, Ss + c * WS_SROW, unit);
                 const float* qr = Qs + (c * G + g) * WS_DH + WS_HALF * half;
                 const float* gr = Gs + (c * G + g) * WS_DH + WS_HALF * half;
                 const float* pr = Ps + (c * G + g) * WS_DH + WS_HF * half;         // sines; the cosines 32 further
@@ -431,8 +374,8 @@ __global__ __launch_bounds__(128 * G) void rel_attn_wide_shared_bwd_dkv_kernel(
                     dp = fmaf(v[4 * d4], gg.x, dp); dp = fmaf(v[4 * d4 + 1], gg.y, dp);
                     dp = fmaf(v[4 * d4 + 2], gg.z, dp); dp = fmaf(v[4 * d4 + 3], gg.w, dp);
                 }
-                s = ws_pair_sum(s);
-                dp = ws_pair_sum(dp);
+                s = rel_pair_sum(s);
+                dp = rel_pair_sum(dp);
                 const float p = exp2f(s - Ls[c * G + g]);
                 const float dS = p * (dp - Ds[c * G + g]);
 #pragma unroll
@@ -448,8 +391,8 @@ __global__ __launch_bounds__(128 * G) void rel_attn_wide_shared_bwd_dkv_kernel(
         }
     }
     if (valid && active) {
-        ws_store_row(dqkv + (long long)kj * lddq + E + crow, dk, scale);
-        ws_store_row(dqkv + (long long)kj * lddq + 2 * E + crow, dv, 1.0f);
+        rel_store_row(dqkv + (long long)kj * lddq + E + crow, dk, scale);
+        rel_store_row(dqkv + (long long)kj * lddq + 2 * E + crow, dv, 1.0f);
     }
 }
 #undef WS_PROLOGUE
@@ -462,49 +405,40 @@ constexpr int WS_LDS_KV = (WS_G * (WS_SROW + 4 * WS_G * WS_DH + 2 * WS_G) + 4 * 
 static_assert(WS_LDS_QK == 73984 && WS_LDS_KV == 82304, "the figures of the file header");
 static_assert(WS_LDS_KV <= 160 * 1024, "one workgroup's LDS");
 
-// more than 64 KB of dynamic LDS has to be asked for once per kernel
-template <typename K>
-static hipError_t ws_allow_lds(K kernel, int bytes) {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-}
-
-hipError_t launch_rel_attn_wide_shared_fwd(const float* qkv, long long ld, const float* qp, long long ldqp, const float* xt,
+hipError_t launch_rel_attn_wide_shared_fwd(const void* qkv, long long ld, const void* qp, long long ldqp, const float* xt,
                                            long long ldxt, const float* freq, int H, int DH, const int* ptr, const int* tile_ptr,
-                                           int B, int N, float* out, long long ldo, float* u, long long ldu, float* lse2,
+                                           int B, int N, void* out, long long ldo, void* u, long long ldu, float* lse2,
                                            hipStream_t st) {
-    if (!rel_attn_wide_shared_supported(DH) || ld % 4 || ldqp % 4 || ldo % 4 || ldu % 4 || ldxt < 4 || ld < 3ll * H * DH ||
-        ldqp < (long long)H * DH || ldo < (long long)H * DH || ldu < (long long)H * DH)
-        return hipErrorInvalidValue;
+    if (!rel_attn_wide_shared_supported(DH) || !rel_args_ok(false, 4, H, DH, ld, ldqp, ldxt, ldo, ldu)) return hipErrorInvalidValue;
     if (N == 0 || B == 0) return hipSuccess;
-    static const hipError_t once = ws_allow_lds(&rel_attn_wide_shared_fwd_kernel<WS_G>, WS_LDS_QK);
+    static const hipError_t once = rel_allow_lds(&rel_attn_wide_shared_fwd_kernel<WS_G>, WS_LDS_QK);
     if (once != hipSuccess) return once;
     const dim3 grid((unsigned)(N / REL_TILE + B), (unsigned)((H + WS_G - 1) / WS_G)), block(128 * WS_G);
-    const float scale2 = REL_LOG2E / sqrtf((float)DH);
-    hipLaunchKernelGGL((rel_attn_wide_shared_fwd_kernel<WS_G>), grid, block, WS_LDS_QK, st, qkv, ld, qp, ldqp, xt, ldxt, freq, H,
-                       ptr, tile_ptr, B, scale2, out, ldo, u, ldu, lse2);
+    hipLaunchKernelGGL((rel_attn_wide_shared_fwd_kernel<WS_G>), grid, block, WS_LDS_QK, st, (const float*)qkv, ld, (const float*)qp,
+                       ldqp, xt, ldxt, freq, H, ptr, tile_ptr, B, rel_scale2(DH), (float*)out, ldo, (float*)u, ldu, lse2);
     return hipGetLastError();
 }
 
-hipError_t launch_rel_attn_wide_shared_bwd(const float* qkv, long long ld, const float* qp, long long ldqp, const float* xt,
+hipError_t launch_rel_attn_wide_shared_bwd(const void* qkv, long long ld, const void* qp, long long ldqp, const float* xt,
                                            long long ldxt, const float* freq, int H, int DH, const int* ptr, const int* tile_ptr,
-                                           int B, int N, const float* out, long long ldo, const float* u, long long ldu,
-                                           const float* dout, long long lddo, const float* du, long long lddu, const float* lse2,
-                                           float* delta, float* dqkv, long long lddq, float* dqp, long long lddqp, hipStream_t st) {
-    const long long d = (long long)H * DH;
-    if (!rel_attn_wide_shared_supported(DH) || ld % 4 || ldqp % 4 || ldo % 4 || ldu % 4 || lddo % 4 || lddu % 4 || lddq % 4 ||
-        lddqp % 4 || ldxt < 4 || ld < 3 * d || lddq < 3 * d || ldqp < d || ldo < d || ldu < d || lddo < d || lddu < d || lddqp < d)
+                                           int B, int N, const void* out, long long ldo, const void* u, long long ldu,
+                                           const void* dout, long long lddo, const void* du, long long lddu, const float* lse2,
+                                           float* delta, void* dqkv, long long lddq, void* dqp, long long lddqp, hipStream_t st) {
+    if (!rel_attn_wide_shared_supported(DH) || !rel_args_ok(true, 4, H, DH, ld, ldqp, ldxt, ldo, ldu, lddo, lddu, lddq, lddqp))
         return hipErrorInvalidValue;
     if (N == 0 || B == 0) return hipSuccess;
-    static const hipError_t once_dq = ws_allow_lds(&rel_attn_wide_shared_bwd_dq_kernel<WS_G>, WS_LDS_QK);
-    static const hipError_t once_kv = ws_allow_lds(&rel_attn_wide_shared_bwd_dkv_kernel<WS_G>, WS_LDS_KV);
+    static const hipError_t once_dq = rel_allow_lds(&rel_attn_wide_shared_bwd_dq_kernel<WS_G>, WS_LDS_QK);
+    static const hipError_t once_kv = rel_allow_lds(&rel_attn_wide_shared_bwd_dkv_kernel<WS_G>, WS_LDS_KV);
     if (once_dq != hipSuccess) return once_dq;
     if (once_kv != hipSuccess) return once_kv;
     const dim3 grid((unsigned)(N / REL_TILE + B), (unsigned)((H + WS_G - 1) / WS_G)), block(128 * WS_G);
-    const float scale = 1.0f / sqrtf((float)DH);
-    hipLaunchKernelGGL((rel_attn_wide_shared_bwd_dq_kernel<WS_G>), grid, block, WS_LDS_QK, st, qkv, ld, qp, ldqp, xt, ldxt, freq,
-                       H, ptr, tile_ptr, B, scale, out, ldo, u, ldu, dout, lddo, du, lddu, lse2, delta, dqkv, lddq, dqp, lddqp);
-    hipLaunchKernelGGL((rel_attn_wide_shared_bwd_dkv_kernel<WS_G>), grid, block, WS_LDS_KV, st, qkv, ld, qp, ldqp, xt, ldxt, freq,
-                       H, ptr, tile_ptr, B, scale, dout, lddo, du, lddu, lse2, delta, dqkv, lddq);
+    const float scale = rel_scale(DH);
+    hipLaunchKernelGGL((rel_attn_wide_shared_bwd_dq_kernel<WS_G>), grid, block, WS_LDS_QK, st, (const float*)qkv, ld,
+                       (const float*)qp, ldqp, xt, ldxt, freq, H, ptr, tile_ptr, B, scale, (const float*)out, ldo, (const float*)u,
+                       ldu, (const float*)dout, lddo, (const float*)du, lddu, lse2, delta, (float*)dqkv, lddq, (float*)dqp, lddqp);
+    hipLaunchKernelGGL((rel_attn_wide_shared_bwd_dkv_kernel<WS_G>), grid, block, WS_LDS_KV, st, (const float*)qkv, ld,
+                       (const float*)qp, ldqp, xt, ldxt, freq, H, ptr, tile_ptr, B, scale, (const float*)dout, lddo,
+                       (const float*)du, lddu, lse2, delta, (float*)dqkv, lddq);
     return hipGetLastError();
 }
 

@@ -668,149 +668,103 @@ int gn_attention_bwd_bits(const void* qkv, int64_t ld, int32_t H, int32_t DH, co
     return fail(r, "gn_attention_bwd_bits");
 }
 
+// ---- ragged attention with the spacetime bias (attn_rel*.hip): six families, one body per pass ----
+static int rel_bad_shape(const char* name, int dh) {
+    char what[128];
+    std::snprintf(what, sizeof(what), "head width %d, row pitches multiples of 16 bytes and at least the row width, xt pitch >= 4", dh);
+    return bad(name, what);
+}
+static int rel_fwd(const char* name, int dh, gn::RelAttnFwd* launch, const void* qkv, int64_t ld, const void* qp, int64_t ldqp,
+                   const float* xt, int64_t ldxt, const float* freq, int32_t H, int32_t DH, const int32_t* ptr,
+                   const int32_t* tile_ptr, int32_t B, int32_t N, void* out, int64_t ldo, void* u, int64_t ldu, float* lse2,
+                   void* stream) {
+    if (H <= 0 || B < 0 || N < 0) return bad(name, "H > 0, B >= 0, N >= 0");
+    if (N > 0 && B > 0 && (!qkv || !qp || !xt || !freq || !ptr || !tile_ptr || !out || !u || !lse2)) return bad(name, "null pointer");
+    hipError_t r = launch(qkv, ld, qp, ldqp, xt, ldxt, freq, H, DH, ptr, tile_ptr, B, N, out, ldo, u, ldu, lse2, S(stream));
+    return r == hipErrorInvalidValue ? rel_bad_shape(name, dh) : fail(r, name);
+}
+static int rel_bwd(const char* name, int dh, gn::RelAttnBwd* launch, const void* qkv, int64_t ld, const void* qp, int64_t ldqp,
+                   const float* xt, int64_t ldxt, const float* freq, int32_t H, int32_t DH, const int32_t* ptr,
+                   const int32_t* tile_ptr, int32_t B, int32_t N, const void* out, int64_t ldo, const void* u, int64_t ldu,
+                   const void* dout, int64_t lddo, const void* du, int64_t lddu, const float* lse2, float* delta, void* dqkv,
+                   int64_t lddq, void* dqp, int64_t lddqp, void* stream) {
+    if (H <= 0 || B < 0 || N < 0) return bad(name, "H > 0, B >= 0, N >= 0");
+    if (N > 0 && B > 0 && (!qkv || !qp || !xt || !freq || !ptr || !tile_ptr || !out || !u || !dout || !du || !lse2 || !delta ||
+                           !dqkv || !dqp))
+        return bad(name, "null pointer");
+    hipError_t r = launch(qkv, ld, qp, ldqp, xt, ldxt, freq, H, DH, ptr, tile_ptr, B, N, out, ldo, u, ldu, dout, lddo, du, lddu,
+                          lse2, delta, dqkv, lddq, dqp, lddqp, S(stream));
+    return r == hipErrorInvalidValue ? rel_bad_shape(name, dh) : fail(r, name);
+}
+
 int gn_rel_attention_supported(int32_t DH) { return gn::rel_attn_supported(DH) ? 1 : 0; }
 int gn_rel_attention_fwd(const float* qkv, int64_t ld, const float* qp, int64_t ldqp, const float* xt, int64_t ldxt,
                          const float* freq, int32_t H, int32_t DH, const int32_t* ptr, const int32_t* tile_ptr, int32_t B,
                          int32_t N, float* out, int64_t ldo, float* u, int64_t ldu, float* lse2, void* stream) {
-    if (H <= 0 || B < 0 || N < 0) return bad("gn_rel_attention_fwd", "H > 0, B >= 0, N >= 0");
-    if (N > 0 && B > 0 && (!qkv || !qp || !xt || !freq || !ptr || !tile_ptr || !out || !u || !lse2))
-        return bad("gn_rel_attention_fwd", "null pointer");
-    hipError_t r = gn::launch_rel_attn_fwd(qkv, ld, qp, ldqp, xt, ldxt, freq, H, DH, ptr, tile_ptr, B, N, out, ldo, u, ldu, lse2,
-                                           S(stream));
-    if (r == hipErrorInvalidValue)
-        return bad("gn_rel_attention_fwd", "head width 32, row pitches multiples of 16 bytes and at least the row width, xt pitch >= 4");
-    return fail(r, "gn_rel_attention_fwd");
+    return rel_fwd("gn_rel_attention_fwd", 32, gn::launch_rel_attn_fwd, qkv, ld, qp, ldqp, xt, ldxt, freq, H, DH, ptr, tile_ptr, B, N, out, ldo, u, ldu, lse2, stream);
 }
 int gn_rel_attention_bwd(const float* qkv, int64_t ld, const float* qp, int64_t ldqp, const float* xt, int64_t ldxt,
                          const float* freq, int32_t H, int32_t DH, const int32_t* ptr, const int32_t* tile_ptr, int32_t B,
                          int32_t N, const float* out, int64_t ldo, const float* u, int64_t ldu, const float* dout,
                          int64_t lddo, const float* du, int64_t lddu, const float* lse2, float* delta, float* dqkv,
                          int64_t lddq, float* dqp, int64_t lddqp, void* stream) {
-    if (H <= 0 || B < 0 || N < 0) return bad("gn_rel_attention_bwd", "H > 0, B >= 0, N >= 0");
-    if (N > 0 && B > 0 && (!qkv || !qp || !xt || !freq || !ptr || !tile_ptr || !out || !u || !dout || !du || !lse2 || !delta ||
-                           !dqkv || !dqp))
-        return bad("gn_rel_attention_bwd", "null pointer");
-    hipError_t r = gn::launch_rel_attn_bwd(qkv, ld, qp, ldqp, xt, ldxt, freq, H, DH, ptr, tile_ptr, B, N, out, ldo, u, ldu, dout,
-                                           lddo, du, lddu, lse2, delta, dqkv, lddq, dqp, lddqp, S(stream));
-    if (r == hipErrorInvalidValue)
-        return bad("gn_rel_attention_bwd", "head width 32, row pitches multiples of 16 bytes and at least the row width, xt pitch >= 4");
-    return fail(r, "gn_rel_attention_bwd");
+    return rel_bwd("gn_rel_attention_bwd", 32, gn::launch_rel_attn_bwd, qkv, ld, qp, ldqp, xt, ldxt, freq, H, DH, ptr, tile_ptr, B, N, out, ldo, u, ldu, dout, lddo, du, lddu, lse2, delta, dqkv, lddq, dqp, lddqp, stream);
 }
 
 int gn_rel_attention_wide_supported(int32_t DH) { return gn::rel_attn_wide_supported(DH) ? 1 : 0; }
 int gn_rel_attention_wide_fwd(const float* qkv, int64_t ld, const float* qp, int64_t ldqp, const float* xt, int64_t ldxt,
                               const float* freq, int32_t H, int32_t DH, const int32_t* ptr, const int32_t* tile_ptr, int32_t B,
                               int32_t N, float* out, int64_t ldo, float* u, int64_t ldu, float* lse2, void* stream) {
-    if (H <= 0 || B < 0 || N < 0) return bad("gn_rel_attention_wide_fwd", "H > 0, B >= 0, N >= 0");
-    if (N > 0 && B > 0 && (!qkv || !qp || !xt || !freq || !ptr || !tile_ptr || !out || !u || !lse2))
-        return bad("gn_rel_attention_wide_fwd", "null pointer");
-    hipError_t r = gn::launch_rel_attn_wide_fwd(qkv, ld, qp, ldqp, xt, ldxt, freq, H, DH, ptr, tile_ptr, B, N, out, ldo, u, ldu, lse2,
-                                                S(stream));
-    if (r == hipErrorInvalidValue)
-        return bad("gn_rel_attention_wide_fwd", "head width 64, row pitches multiples of 16 bytes and at least the row width, xt pitch >= 4");
-    return fail(r, "gn_rel_attention_wide_fwd");
+    return rel_fwd("gn_rel_attention_wide_fwd", 64, gn::launch_rel_attn_wide_fwd, qkv, ld, qp, ldqp, xt, ldxt, freq, H, DH, ptr, tile_ptr, B, N, out, ldo, u, ldu, lse2, stream);
 }
 int gn_rel_attention_wide_bwd(const float* qkv, int64_t ld, const float* qp, int64_t ldqp, const float* xt, int64_t ldxt,
                               const float* freq, int32_t H, int32_t DH, const int32_t* ptr, const int32_t* tile_ptr, int32_t B,
                               int32_t N, const float* out, int64_t ldo, const float* u, int64_t ldu, const float* dout,
                               int64_t lddo, const float* du, int64_t lddu, const float* lse2, float* delta, float* dqkv,
                               int64_t lddq, float* dqp, int64_t lddqp, void* stream) {
-    if (H <= 0 || B < 0 || N < 0) return bad("gn_rel_attention_wide_bwd", "H > 0, B >= 0, N >= 0");
-    if (N > 0 && B > 0 && (!qkv || !qp || !xt || !freq || !ptr || !tile_ptr || !out || !u || !dout || !du || !lse2 || !delta ||
-                                !dqkv || !dqp))
-        return bad("gn_rel_attention_wide_bwd", "null pointer");
-    hipError_t r = gn::launch_rel_attn_wide_bwd(qkv, ld, qp, ldqp, xt, ldxt, freq, H, DH, ptr, tile_ptr, B, N, out, ldo, u, ldu, dout,
-                                                lddo, du, lddu, lse2, delta, dqkv, lddq, dqp, lddqp, S(stream));
-    if (r == hipErrorInvalidValue)
-        return bad("gn_rel_attention_wide_bwd", "head width 64, row pitches multiples of 16 bytes and at least the row width, xt pitch >= 4");
-    return fail(r, "gn_rel_attention_wide_bwd");
+    return rel_bwd("gn_rel_attention_wide_bwd", 64, gn::launch_rel_attn_wide_bwd, qkv, ld, qp, ldqp, xt, ldxt, freq, H, DH, ptr, tile_ptr, B, N, out, ldo, u, ldu, dout, lddo, du, lddu, lse2, delta, dqkv, lddq, dqp, lddqp, stream);
 }
 
 int gn_rel_attention_shared_supported(int32_t DH) { return gn::rel_attn_shared_supported(DH) ? 1 : 0; }
 int gn_rel_attention_shared_fwd(const float* qkv, int64_t ld, const float* qp, int64_t ldqp, const float* xt, int64_t ldxt,
-                              const float* freq, int32_t H, int32_t DH, const int32_t* ptr, const int32_t* tile_ptr, int32_t B,
-                              int32_t N, float* out, int64_t ldo, float* u, int64_t ldu, float* lse2, void* stream) {
-    if (H <= 0 || B < 0 || N < 0) return bad("gn_rel_attention_shared_fwd", "H > 0, B >= 0, N >= 0");
-    if (N > 0 && B > 0 && (!qkv || !qp || !xt || !freq || !ptr || !tile_ptr || !out || !u || !lse2))
-        return bad("gn_rel_attention_shared_fwd", "null pointer");
-    hipError_t r = gn::launch_rel_attn_shared_fwd(qkv, ld, qp, ldqp, xt, ldxt, freq, H, DH, ptr, tile_ptr, B, N, out, ldo, u, ldu, lse2,
-                                                S(stream));
-    if (r == hipErrorInvalidValue)
-        return bad("gn_rel_attention_shared_fwd", "head width 32, row pitches multiples of 16 bytes and at least the row width, xt pitch >= 4");
-    return fail(r, "gn_rel_attention_shared_fwd");
+                                const float* freq, int32_t H, int32_t DH, const int32_t* ptr, const int32_t* tile_ptr, int32_t B,
+                                int32_t N, float* out, int64_t ldo, float* u, int64_t ldu, float* lse2, void* stream) {
+    return rel_fwd("gn_rel_attention_shared_fwd", 32, gn::launch_rel_attn_shared_fwd, qkv, ld, qp, ldqp, xt, ldxt, freq, H, DH, ptr, tile_ptr, B, N, out, ldo, u, ldu, lse2, stream);
 }
 int gn_rel_attention_shared_bwd(const float* qkv, int64_t ld, const float* qp, int64_t ldqp, const float* xt, int64_t ldxt,
-                              const float* freq, int32_t H, int32_t DH, const int32_t* ptr, const int32_t* tile_ptr, int32_t B,
-                              int32_t N, const float* out, int64_t ldo, const float* u, int64_t ldu, const float* dout,
-                              int64_t lddo, const float* du, int64_t lddu, const float* lse2, float* delta, float* dqkv,
-                              int64_t lddq, float* dqp, int64_t lddqp, void* stream) {
-    if (H <= 0 || B < 0 || N < 0) return bad("gn_rel_attention_shared_bwd", "H > 0, B >= 0, N >= 0");
-    if (N > 0 && B > 0 && (!qkv || !qp || !xt || !freq || !ptr || !tile_ptr || !out || !u || !dout || !du || !lse2 || !delta ||
-                                !dqkv || !dqp))
-        return bad("gn_rel_attention_shared_bwd", "null pointer");
-    hipError_t r = gn::launch_rel_attn_shared_bwd(qkv, ld, qp, ldqp, xt, ldxt, freq, H, DH, ptr, tile_ptr, B, N, out, ldo, u, ldu, dout,
-                                                lddo, du, lddu, lse2, delta, dqkv, lddq, dqp, lddqp, S(stream));
-    if (r == hipErrorInvalidValue)
-        return bad("gn_rel_attention_shared_bwd", "head width 32, row pitches multiples of 16 bytes and at least the row width, xt pitch >= 4");
-    return fail(r, "gn_rel_attention_shared_bwd");
+                                const float* freq, int32_t H, int32_t DH, const int32_t* ptr, const int32_t* tile_ptr, int32_t B,
+                                int32_t N, const float* out, int64_t ldo, const float* u, int64_t ldu, const float* dout,
+                                int64_t lddo, const float* du, int64_t lddu, const float* lse2, float* delta, float* dqkv,
+                                int64_t lddq, float* dqp, int64_t lddqp, void* stream) {
+    return rel_bwd("gn_rel_attention_shared_bwd", 32, gn::launch_rel_attn_shared_bwd, qkv, ld, qp, ldqp, xt, ldxt, freq, H, DH, ptr, tile_ptr, B, N, out, ldo, u, ldu, dout, lddo, du, lddu, lse2, delta, dqkv, lddq, dqp, lddqp, stream);
 }
 
 int gn_rel_attention_mfma_supported(int32_t DH) { return gn::rel_attn_mfma_supported(DH) ? 1 : 0; }
 int gn_rel_attention_mfma_fwd(const void* qkv, int64_t ld, const void* qp, int64_t ldqp, const float* xt, int64_t ldxt,
                               const float* freq, int32_t H, int32_t DH, const int32_t* ptr, const int32_t* tile_ptr, int32_t B,
                               int32_t N, void* out, int64_t ldo, void* u, int64_t ldu, float* lse2, void* stream) {
-    if (H <= 0 || B < 0 || N < 0) return bad("gn_rel_attention_mfma_fwd", "H > 0, B >= 0, N >= 0");
-    if (N > 0 && B > 0 && (!qkv || !qp || !xt || !freq || !ptr || !tile_ptr || !out || !u || !lse2))
-        return bad("gn_rel_attention_mfma_fwd", "null pointer");
-    hipError_t r = gn::launch_rel_attn_mfma_fwd(qkv, ld, qp, ldqp, xt, ldxt, freq, H, DH, ptr, tile_ptr, B, N, out, ldo, u, ldu, lse2,
-                                                S(stream));
-    if (r == hipErrorInvalidValue)
-        return bad("gn_rel_attention_mfma_fwd", "head width 32, row pitches multiples of 16 bytes and at least the row width, xt pitch >= 4");
-    return fail(r, "gn_rel_attention_mfma_fwd");
+    return rel_fwd("gn_rel_attention_mfma_fwd", 32, gn::launch_rel_attn_mfma_fwd, qkv, ld, qp, ldqp, xt, ldxt, freq, H, DH, ptr, tile_ptr, B, N, out, ldo, u, ldu, lse2, stream);
 }
 int gn_rel_attention_mfma_bwd(const void* qkv, int64_t ld, const void* qp, int64_t ldqp, const float* xt, int64_t ldxt,
                               const float* freq, int32_t H, int32_t DH, const int32_t* ptr, const int32_t* tile_ptr, int32_t B,
                               int32_t N, const void* out, int64_t ldo, const void* u, int64_t ldu, const void* dout,
                               int64_t lddo, const void* du, int64_t lddu, const float* lse2, float* delta, void* dqkv,
                               int64_t lddq, void* dqp, int64_t lddqp, void* stream) {
-    if (H <= 0 || B < 0 || N < 0) return bad("gn_rel_attention_mfma_bwd", "H > 0, B >= 0, N >= 0");
-    if (N > 0 && B > 0 && (!qkv || !qp || !xt || !freq || !ptr || !tile_ptr || !out || !u || !dout || !du || !lse2 || !delta ||
-                                !dqkv || !dqp))
-        return bad("gn_rel_attention_mfma_bwd", "null pointer");
-    hipError_t r = gn::launch_rel_attn_mfma_bwd(qkv, ld, qp, ldqp, xt, ldxt, freq, H, DH, ptr, tile_ptr, B, N, out, ldo, u, ldu, dout,
-                                                lddo, du, lddu, lse2, delta, dqkv, lddq, dqp, lddqp, S(stream));
-    if (r == hipErrorInvalidValue)
-        return bad("gn_rel_attention_mfma_bwd", "head width 32, row pitches multiples of 16 bytes and at least the row width, xt pitch >= 4");
-    return fail(r, "gn_rel_attention_mfma_bwd");
+    return rel_bwd("gn_rel_attention_mfma_bwd", 32, gn::launch_rel_attn_mfma_bwd, qkv, ld, qp, ldqp, xt, ldxt, freq, H, DH, ptr, tile_ptr, B, N, out, ldo, u, ldu, dout, lddo, du, lddu, lse2, delta, dqkv, lddq, dqp, lddqp, stream);
 }
 
 int gn_rel_attention_mfma_wide_supported(int32_t DH) { return gn::rel_attn_mfma_wide_supported(DH) ? 1 : 0; }
 int gn_rel_attention_mfma_wide_fwd(const void* qkv, int64_t ld, const void* qp, int64_t ldqp, const float* xt, int64_t ldxt,
                                    const float* freq, int32_t H, int32_t DH, const int32_t* ptr, const int32_t* tile_ptr,
                                    int32_t B, int32_t N, void* out, int64_t ldo, void* u, int64_t ldu, float* lse2, void* stream) {
-    if (H <= 0 || B < 0 || N < 0) return bad("gn_rel_attention_mfma_wide_fwd", "H > 0, B >= 0, N >= 0");
-    if (N > 0 && B > 0 && (!qkv || !qp || !xt || !freq || !ptr || !tile_ptr || !out || !u || !lse2))
-        return bad("gn_rel_attention_mfma_wide_fwd", "null pointer");
-    hipError_t r = gn::launch_rel_attn_mfma_wide_fwd(qkv, ld, qp, ldqp, xt, ldxt, freq, H, DH, ptr, tile_ptr, B, N, out, ldo, u, ldu,
-                                                     lse2, S(stream));
-    if (r == hipErrorInvalidValue)
-        return bad("gn_rel_attention_mfma_wide_fwd", "head width 64, row pitches multiples of 16 bytes and at least the row width, xt pitch >= 4");
-    return fail(r, "gn_rel_attention_mfma_wide_fwd");
+    return rel_fwd("gn_rel_attention_mfma_wide_fwd", 64, gn::launch_rel_attn_mfma_wide_fwd, qkv, ld, qp, ldqp, xt, ldxt, freq, H, DH, ptr, tile_ptr, B, N, out, ldo, u, ldu, lse2, stream);
 }
 int gn_rel_attention_mfma_wide_bwd(const void* qkv, int64_t ld, const void* qp, int64_t ldqp, const float* xt, int64_t ldxt,
                                    const float* freq, int32_t H, int32_t DH, const int32_t* ptr, const int32_t* tile_ptr,
                                    int32_t B, int32_t N, const void* out, int64_t ldo, const void* u, int64_t ldu,
                                    const void* dout, int64_t lddo, const void* du, int64_t lddu, const float* lse2, float* delta,
                                    void* dqkv, int64_t lddq, void* dqp, int64_t lddqp, void* stream) {
-    if (H <= 0 || B < 0 || N < 0) return bad("gn_rel_attention_mfma_wide_bwd", "H > 0, B >= 0, N >= 0");
-    if (N > 0 && B > 0 && (!qkv || !qp || !xt || !freq || !ptr || !tile_ptr || !out || !u || !dout || !du || !lse2 || !delta ||
-                                !dqkv || !dqp))
-        return bad("gn_rel_attention_mfma_wide_bwd", "null pointer");
-    hipError_t r = gn::launch_rel_attn_mfma_wide_bwd(qkv, ld, qp, ldqp, xt, ldxt, freq, H, DH, ptr, tile_ptr, B, N, out, ldo, u, ldu,
-                                                     dout, lddo, du, lddu, lse2, delta, dqkv, lddq, dqp, lddqp, S(stream));
-    if (r == hipErrorInvalidValue)
-        return bad("gn_rel_attention_mfma_wide_bwd", "head width 64, row pitches multiples of 16 bytes and at least the row width, xt pitch >= 4");
-    return fail(r, "gn_rel_attention_mfma_wide_bwd");
+    return rel_bwd("gn_rel_attention_mfma_wide_bwd", 64, gn::launch_rel_attn_mfma_wide_bwd, qkv, ld, qp, ldqp, xt, ldxt, freq, H, DH, ptr, tile_ptr, B, N, out, ldo, u, ldu, dout, lddo, du, lddu, lse2, delta, dqkv, lddq, dqp, lddqp, stream);
 }
 
 int gn_rel_attention_wide_shared_supported(int32_t DH) { return gn::rel_attn_wide_shared_supported(DH) ? 1 : 0; }
@@ -818,29 +772,14 @@ int gn_rel_attention_wide_shared_fwd(const float* qkv, int64_t ld, const float* 
                                      const float* freq, int32_t H, int32_t DH, const int32_t* ptr, const int32_t* tile_ptr,
                                      int32_t B, int32_t N, float* out, int64_t ldo, float* u, int64_t ldu, float* lse2,
                                      void* stream) {
-    if (H <= 0 || B < 0 || N < 0) return bad("gn_rel_attention_wide_shared_fwd", "H > 0, B >= 0, N >= 0");
-    if (N > 0 && B > 0 && (!qkv || !qp || !xt || !freq || !ptr || !tile_ptr || !out || !u || !lse2))
-        return bad("gn_rel_attention_wide_shared_fwd", "null pointer");
-    hipError_t r = gn::launch_rel_attn_wide_shared_fwd(qkv, ld, qp, ldqp, xt, ldxt, freq, H, DH, ptr, tile_ptr, B, N, out, ldo, u, ldu,
-                                                       lse2, S(stream));
-    if (r == hipErrorInvalidValue)
-        return bad("gn_rel_attention_wide_shared_fwd", "head width 64, row pitches multiples of 16 bytes and at least the row width, xt pitch >= 4");
-    return fail(r, "gn_rel_attention_wide_shared_fwd");
+    return rel_fwd("gn_rel_attention_wide_shared_fwd", 64, gn::launch_rel_attn_wide_shared_fwd, qkv, ld, qp, ldqp, xt, ldxt, freq, H, DH, ptr, tile_ptr, B, N, out, ldo, u, ldu, lse2, stream);
 }
 int gn_rel_attention_wide_shared_bwd(const float* qkv, int64_t ld, const float* qp, int64_t ldqp, const float* xt, int64_t ldxt,
                                      const float* freq, int32_t H, int32_t DH, const int32_t* ptr, const int32_t* tile_ptr,
                                      int32_t B, int32_t N, const float* out, int64_t ldo, const float* u, int64_t ldu,
                                      const float* dout, int64_t lddo, const float* du, int64_t lddu, const float* lse2,
                                      float* delta, float* dqkv, int64_t lddq, float* dqp, int64_t lddqp, void* stream) {
-    if (H <= 0 || B < 0 || N < 0) return bad("gn_rel_attention_wide_shared_bwd", "H > 0, B >= 0, N >= 0");
-    if (N > 0 && B > 0 && (!qkv || !qp || !xt || !freq || !ptr || !tile_ptr || !out || !u || !dout || !du || !lse2 || !delta ||
-                                !dqkv || !dqp))
-        return bad("gn_rel_attention_wide_shared_bwd", "null pointer");
-    hipError_t r = gn::launch_rel_attn_wide_shared_bwd(qkv, ld, qp, ldqp, xt, ldxt, freq, H, DH, ptr, tile_ptr, B, N, out, ldo, u, ldu,
-                                                       dout, lddo, du, lddu, lse2, delta, dqkv, lddq, dqp, lddqp, S(stream));
-    if (r == hipErrorInvalidValue)
-        return bad("gn_rel_attention_wide_shared_bwd", "head width 64, row pitches multiples of 16 bytes and at least the row width, xt pitch >= 4");
-    return fail(r, "gn_rel_attention_wide_shared_bwd");
+    return rel_bwd("gn_rel_attention_wide_shared_bwd", 64, gn::launch_rel_attn_wide_shared_bwd, qkv, ld, qp, ldqp, xt, ldxt, freq, H, DH, ptr, tile_ptr, B, N, out, ldo, u, ldu, dout, lddo, du, lddu, lse2, delta, dqkv, lddq, dqp, lddqp, stream);
 }
 
 int gn_dropout(const void* x, int64_t ldx, int32_t x_lowp, const float* res, int64_t ldres, void* y, int64_t ldy,

@@ -187,67 +187,40 @@ hipError_t launch_attn_bwd(int lowp, const void* qkv, long long ld, int H, int D
                            const float* lse2, float* delta, void* dqkv, long long lddq, unsigned seed, unsigned thresh,
                            const unsigned int* bits_r, const unsigned int* bits_c, const long long* evoff, long long plane,
                            hipStream_t st);
-// attn_rel.hip: ragged attention with the spacetime bias of DeepIce recomputed per pair (fp32, head width 32)
+// attn_rel*.hip: ragged attention with the spacetime bias of DeepIce recomputed per pair, six kernel families behind two
+// signatures.  Rows (qkv, qp, out, u, dout, du, dqkv, dqp) are fp32 or, in the mfma families, bf16; row pitches in elements.
+using RelAttnFwd = hipError_t(const void* qkv, long long ld, const void* qp, long long ldqp, const float* xt, long long ldxt,
+                              const float* freq, int H, int DH, const int* ptr, const int* tile_ptr, int B, int N, void* out,
+                              long long ldo, void* u, long long ldu, float* lse2, hipStream_t st);
+using RelAttnBwd = hipError_t(const void* qkv, long long ld, const void* qp, long long ldqp, const float* xt, long long ldxt,
+                              const float* freq, int H, int DH, const int* ptr, const int* tile_ptr, int B, int N,
+                              const void* out, long long ldo, const void* u, long long ldu, const void* dout, long long lddo,
+                              const void* du, long long lddu, const float* lse2, float* delta, void* dqkv, long long lddq,
+                              void* dqp, long long lddqp, hipStream_t st);
+// attn_rel.hip: fp32, head width 32, one lane per query / key
 bool rel_attn_supported(int DH);
-hipError_t launch_rel_attn_fwd(const float* qkv, long long ld, const float* qp, long long ldqp, const float* xt, long long ldxt,
-                               const float* freq, int H, int DH, const int* ptr, const int* tile_ptr, int B, int N,
-                               float* out, long long ldo, float* u, long long ldu, float* lse2, hipStream_t st);
-hipError_t launch_rel_attn_bwd(const float* qkv, long long ld, const float* qp, long long ldqp, const float* xt, long long ldxt,
-                               const float* freq, int H, int DH, const int* ptr, const int* tile_ptr, int B, int N,
-                               const float* out, long long ldo, const float* u, long long ldu, const float* dout,
-                               long long lddo, const float* du, long long lddu, const float* lse2, float* delta,
-                               float* dqkv, long long lddq, float* dqp, long long lddqp, hipStream_t st);
-// attn_rel_wide.hip: the same for head width 64, two lanes per query / key (arguments as above)
+RelAttnFwd launch_rel_attn_fwd;
+RelAttnBwd launch_rel_attn_bwd;
+// attn_rel_wide.hip: fp32, head width 64, two lanes per query / key
 bool rel_attn_wide_supported(int DH);
-hipError_t launch_rel_attn_wide_fwd(const float* qkv, long long ld, const float* qp, long long ldqp, const float* xt,
-                                    long long ldxt, const float* freq, int H, int DH, const int* ptr, const int* tile_ptr, int B,
-                                    int N, float* out, long long ldo, float* u, long long ldu, float* lse2, hipStream_t st);
-hipError_t launch_rel_attn_wide_bwd(const float* qkv, long long ld, const float* qp, long long ldqp, const float* xt,
-                                    long long ldxt, const float* freq, int H, int DH, const int* ptr, const int* tile_ptr, int B,
-                                    int N, const float* out, long long ldo, const float* u, long long ldu, const float* dout,
-                                    long long lddo, const float* du, long long lddu, const float* lse2, float* delta,
-                                    float* dqkv, long long lddq, float* dqp, long long lddqp, hipStream_t st);
-// attn_rel_shared.hip: head width 32 with s_ij formed once per pair for a group of heads (arguments as above)
+RelAttnFwd launch_rel_attn_wide_fwd;
+RelAttnBwd launch_rel_attn_wide_bwd;
+// attn_rel_shared.hip: fp32, head width 32, s_ij formed once per pair for a group of heads
 bool rel_attn_shared_supported(int DH);
-hipError_t launch_rel_attn_shared_fwd(const float* qkv, long long ld, const float* qp, long long ldqp, const float* xt,
-                                      long long ldxt, const float* freq, int H, int DH, const int* ptr, const int* tile_ptr, int B,
-                                      int N, float* out, long long ldo, float* u, long long ldu, float* lse2, hipStream_t st);
-hipError_t launch_rel_attn_shared_bwd(const float* qkv, long long ld, const float* qp, long long ldqp, const float* xt,
-                                      long long ldxt, const float* freq, int H, int DH, const int* ptr, const int* tile_ptr, int B,
-                                      int N, const float* out, long long ldo, const float* u, long long ldu, const float* dout,
-                                      long long lddo, const float* du, long long lddu, const float* lse2, float* delta,
-                                      float* dqkv, long long lddq, float* dqp, long long lddqp, hipStream_t st);
-// attn_rel_mfma.hip: head width 32, bf16 operands on the matrix cores (qkv, qp, out, u, dout, du, dqkv, dqp bf16; pitches in elements)
+RelAttnFwd launch_rel_attn_shared_fwd;
+RelAttnBwd launch_rel_attn_shared_bwd;
+// attn_rel_wide_shared.hip: fp32, head width 64, two lanes per query / key, s_ij formed once per pair for a group of heads
+bool rel_attn_wide_shared_supported(int DH);
+RelAttnFwd launch_rel_attn_wide_shared_fwd;
+RelAttnBwd launch_rel_attn_wide_shared_bwd;
+// attn_rel_mfma.hip: bf16 operands on the matrix cores, head width 32
 bool rel_attn_mfma_supported(int DH);
-hipError_t launch_rel_attn_mfma_fwd(const void* qkv, long long ld, const void* qp, long long ldqp, const float* xt, long long ldxt,
-                                    const float* freq, int H, int DH, const int* ptr, const int* tile_ptr, int B, int N, void* out,
-                                    long long ldo, void* u, long long ldu, float* lse2, hipStream_t st);
-hipError_t launch_rel_attn_mfma_bwd(const void* qkv, long long ld, const void* qp, long long ldqp, const float* xt, long long ldxt,
-                                    const float* freq, int H, int DH, const int* ptr, const int* tile_ptr, int B, int N,
-                                    const void* out, long long ldo, const void* u, long long ldu, const void* dout, long long lddo,
-                                    const void* du, long long lddu, const float* lse2, float* delta, void* dqkv, long long lddq,
-                                    void* dqp, long long lddqp, hipStream_t st);
+RelAttnFwd launch_rel_attn_mfma_fwd;
+RelAttnBwd launch_rel_attn_mfma_bwd;
 // attn_rel_mfma_wide.hip: the same at head width 64 (a workgroup owns 16 rows, two threads form each pair's s_ij)
 bool rel_attn_mfma_wide_supported(int DH);
-hipError_t launch_rel_attn_mfma_wide_fwd(const void* qkv, long long ld, const void* qp, long long ldqp, const float* xt,
-                                         long long ldxt, const float* freq, int H, int DH, const int* ptr, const int* tile_ptr, int B,
-                                         int N, void* out, long long ldo, void* u, long long ldu, float* lse2, hipStream_t st);
-hipError_t launch_rel_attn_mfma_wide_bwd(const void* qkv, long long ld, const void* qp, long long ldqp, const float* xt,
-                                         long long ldxt, const float* freq, int H, int DH, const int* ptr, const int* tile_ptr, int B,
-                                         int N, const void* out, long long ldo, const void* u, long long ldu, const void* dout,
-                                         long long lddo, const void* du, long long lddu, const float* lse2, float* delta, void* dqkv,
-                                         long long lddq, void* dqp, long long lddqp, hipStream_t st);
-// attn_rel_wide_shared.hip: head width 64 in fp32 with s_ij formed once per pair for a group of heads (arguments as attn_rel_wide.hip)
-bool rel_attn_wide_shared_supported(int DH);
-hipError_t launch_rel_attn_wide_shared_fwd(const float* qkv, long long ld, const float* qp, long long ldqp, const float* xt,
-                                           long long ldxt, const float* freq, int H, int DH, const int* ptr, const int* tile_ptr,
-                                           int B, int N, float* out, long long ldo, float* u, long long ldu, float* lse2,
-                                           hipStream_t st);
-hipError_t launch_rel_attn_wide_shared_bwd(const float* qkv, long long ld, const float* qp, long long ldqp, const float* xt,
-                                           long long ldxt, const float* freq, int H, int DH, const int* ptr, const int* tile_ptr,
-                                           int B, int N, const float* out, long long ldo, const float* u, long long ldu,
-                                           const float* dout, long long lddo, const float* du, long long lddu, const float* lse2,
-                                           float* delta, float* dqkv, long long lddq, float* dqp, long long lddqp, hipStream_t st);
+RelAttnFwd launch_rel_attn_mfma_wide_fwd;
+RelAttnBwd launch_rel_attn_mfma_wide_bwd;
 // tagconv.hip: TAGConv(K = 2) - normalised-adjacency propagation, its transpose and the fused layer (fp32 rows, widths % 32, <= 256)
 bool tagconv_supported(int C_in, int C_out);
 hipError_t launch_tag_norm(const int* nbr, const int* ovf, int N, int K, float* dis, hipStream_t st);

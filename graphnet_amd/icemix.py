@@ -5,10 +5,9 @@ constructor signatures, defaults and sub-module names, hence the same state-dict
 ``[B, L, d]``, materialises the spacetime bias as ``[B, L, L, head_size]`` fp32 and contracts it twice per layer.  Here the
 batch stays ragged (``x``, ``ptr``) and neither tensor exists:
 
-* blocks with the spacetime bias run on ``csrc/attn_rel.hip`` (head width 32; with ``Attention_rel.shared_bias`` on
-  ``csrc/attn_rel_shared.hip``; in bf16 mode with ``Attention_rel.matrix_bias`` on ``csrc/attn_rel_mfma.hip``) or
-  ``csrc/attn_rel_wide.hip`` (64; with ``Attention_rel.shared_bias`` on ``csrc/attn_rel_wide_shared.hip``; in bf16 mode with
-  ``Attention_rel.matrix_bias`` on ``csrc/attn_rel_mfma_wide.hip``).
+* blocks with the spacetime bias run on one of the six kernel families of ``csrc/attn_rel*.hip`` (head widths 32 and 64);
+  ``ops._REL_FAMILY`` describes them and ``ops.rel_attention_family`` chooses one from the head width,
+  ``Attention_rel.shared_bias`` and, in bf16 mode, ``Attention_rel.matrix_bias``.
   With ``s_ij`` the sinusoidal embedding of the clipped 4-distance and ``R_ij = W s_ij + b`` (``rel_pos.projection``), ``q~ . k + q~ . R_ij = q~ . k + (W^T q~) . s_ij + const`` and
   ``sum_j a_ij (v_j + R_ij) = O_i + W U_i + b`` with ``U_i = sum_j a_ij s_ij``: the kernel takes ``q, k, v`` and ``q' = W^T q~``,
   recomputes ``s_ij`` per pair and returns ``O`` and ``U``; ``W`` and ``b`` stay in two small GEMMs with plain autograd;
@@ -53,30 +52,18 @@ class _RaggedAttentionFunction(torch.autograd.Function):
 
 class _RelAttentionFunction(torch.autograd.Function):
     """Ragged attention with the spacetime bias recomputed per pair: (qkv ``[N, 3 d]``, qp ``[N, d]``) -> (out, u), both
-    ``[N, d]``; ``xt`` and ``freq`` are data.  Head width 64 runs on ``ops.rel_attention_wide_*``, head width 32 on
-    ``ops.rel_attention_*``; with ``shared`` (``Attention_rel.shared_bias``) they run on ``ops.rel_attention_wide_shared_*`` and
-    ``ops.rel_attention_shared_*``, which give the same bits; with
-    ``matrix`` (``Attention_rel.matrix_bias`` in bf16 mode: bf16 ``qkv`` and ``qp``) on ``ops.rel_attention_mfma_*`` (head width 32)
-    or ``ops.rel_attention_mfma_wide_*`` (64)."""
+    ``[N, d]``; ``xt`` and ``freq`` are data.  The kernel family is ``ops.rel_attention_family(dh, shared=, matrix=)``
+    (``shared``: ``Attention_rel.shared_bias``; ``matrix``: ``Attention_rel.matrix_bias`` in bf16 mode, bf16 ``qkv`` and ``qp``).
+    A head width that no family is built for goes to the per-head family of the mode, which raises."""
 
     @staticmethod
     def forward(ctx, qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, ptr: Tensor, plan: Tensor,
                 shared: bool = False, matrix: bool = False):  # type: ignore[override]
         qkv, qp = qkv.contiguous(), qp.contiguous()
         dh = int(qp.shape[1]) // n_head
-        if matrix and ops.rel_attention_mfma_wide_supported(dh):
-            fwd, ctx.bwd = ops.rel_attention_mfma_wide_fwd, ops.rel_attention_mfma_wide_bwd
-        elif matrix:
-            fwd, ctx.bwd = ops.rel_attention_mfma_fwd, ops.rel_attention_mfma_bwd
-        elif shared and ops.rel_attention_wide_shared_supported(dh):
-            fwd, ctx.bwd = ops.rel_attention_wide_shared_fwd, ops.rel_attention_wide_shared_bwd
-        elif ops.rel_attention_wide_supported(dh):
-            fwd, ctx.bwd = ops.rel_attention_wide_fwd, ops.rel_attention_wide_bwd
-        elif shared and ops.rel_attention_shared_supported(dh):
-            fwd, ctx.bwd = ops.rel_attention_shared_fwd, ops.rel_attention_shared_bwd
-        else:
-            fwd, ctx.bwd = ops.rel_attention_fwd, ops.rel_attention_bwd
-        out, u, lse2 = fwd(qkv, qp, xt, freq, n_head, ptr, plan)
+        family = ops.rel_attention_family(dh, shared=shared, matrix=matrix)
+        ctx.family = family or ("rel_attention_mfma" if matrix else "rel_attention")
+        out, u, lse2 = ops.rel_attention_run_fwd(ctx.family, qkv, qp, xt, freq, n_head, ptr, plan)
         ctx.save_for_backward(qkv, qp, xt, freq, ptr, plan, out, u, lse2)
         ctx.n_head = n_head
         return out, u
@@ -84,14 +71,14 @@ class _RelAttentionFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout: Tensor, du: Tensor):  # type: ignore[override]
         qkv, qp, xt, freq, ptr, plan, out, u, lse2 = ctx.saved_tensors
-        dqkv, dqp = ctx.bwd(qkv, qp, xt, freq, ctx.n_head, ptr, plan, out, u, lse2, dout.contiguous().to(qkv.dtype),
-                            du.contiguous().to(qkv.dtype))
+        dqkv, dqp = ops.rel_attention_run_bwd(ctx.family, qkv, qp, xt, freq, ctx.n_head, ptr, plan, out, u, lse2,
+                                              dout.contiguous().to(qkv.dtype), du.contiguous().to(qkv.dtype))
         return dqkv, dqp, None, None, None, None, None, None, None
 
 
 def _rel_width_built(dh: int) -> bool:
-    """Head widths of the biased attention: 32 (one lane per query) and 64 (two lanes per query)."""
-    return ops.rel_attention_supported(dh) or ops.rel_attention_wide_supported(dh)
+    """Head widths of the biased attention: those ``ops.rel_attention_family`` has a family for (32 and 64)."""
+    return ops.rel_attention_family(dh) is not None
 
 
 def _linear(x: Tensor, weight: Tensor, bias: Optional[Tensor], mode: int) -> Tensor:
@@ -292,8 +279,7 @@ class Attention_rel(Model):
             if not _rel_width_built(dh):
                 raise NotImplementedError(f"graphnet_amd.Attention_rel: the biased attention kernels are built for head widths "
                                           f"32 and 64, not {dh}; there is no fallback")
-            matrix = self.matrix_bias and mode == ops.MODE_BF16 and (ops.rel_attention_mfma_supported(dh) or
-                                                                     ops.rel_attention_mfma_wide_supported(dh))
+            matrix = self.matrix_bias and mode == ops.MODE_BF16 and ops.rel_attention_family(dh, matrix=True) is not None
             Wr, br = rel.projection.weight, rel.projection.bias                  # R_ij = Wr s_ij + br
             if matrix:                                                           # qkv stays bf16; qp in fp32, rounded once
                 qp = torch.matmul(qkv[:, :d].to(torch.float32).reshape(N, H, dh) * self.scale, Wr).reshape(N, d).to(torch.bfloat16)

@@ -1383,11 +1383,6 @@ def attention_bwd(qkv: Tensor, n_head: int, ptr: Tensor, plan: Tensor, out: Tens
 
 
 # ------------------------------------------------------------------------------ ragged attention + spacetime bias (DeepIce)
-def rel_attention_supported(dh: int) -> bool:
-    """Head widths of the biased attention kernels (``gn_rel_attention_supported``)."""
-    return bool(_lib.lib().gn_rel_attention_supported(int(dh)))
-
-
 def rel_attention_freq(dh: int, device) -> Tensor:
     """The ``dh / 2`` frequencies of ``SinusoidalPosEmb(dh)``: the fp32 operations of ``rnn.sinusoidal_pos_emb``, on the host."""
     half_dim = dh / 2
@@ -1395,51 +1390,52 @@ def rel_attention_freq(dh: int, device) -> Tensor:
     return torch.exp(torch.arange(half_dim) * (-emb)).to(device)
 
 
-def rel_attention_wide_supported(dh: int) -> bool:
-    """Head widths of the two-lanes-per-query biased attention kernels (``gn_rel_attention_wide_supported``): 64."""
-    return bool(_lib.lib().gn_rel_attention_wide_supported(int(dh)))
+@dataclass(frozen=True)
+class _RelFamily:
+    """One kernel family of the biased attention.  Its key in ``_REL_FAMILY`` is the stem of its three C entries
+    (``gn_<stem>_supported`` / ``_fwd`` / ``_bwd``) and of its three functions here."""
+    what: str             # what the "not built" message calls it
+    built: int            # the head width it is built for
+    rows: torch.dtype     # type of qkv, qp, out, u, dout, du and the gradients (xt, freq, lse2 are fp32 in every family)
+    shared: bool          # s_ij is formed once per pair for a group of heads; the same bits as the per-head family of the width
+    matrix: bool          # bf16 operands on the matrix cores
+    doc: str              # one line for the docstrings of its functions
 
 
-def rel_attention_shared_supported(dh: int) -> bool:
-    """Head widths of the biased attention kernels that form ``s_ij`` once per pair for a group of heads
-    (``gn_rel_attention_shared_supported``): 32."""
-    return bool(_lib.lib().gn_rel_attention_shared_supported(int(dh)))
-
-
-def rel_attention_mfma_supported(dh: int) -> bool:
-    """Head widths of the biased attention kernels with bf16 operands on the matrix cores
-    (``gn_rel_attention_mfma_supported``): 32."""
-    return bool(_lib.lib().gn_rel_attention_mfma_supported(int(dh)))
-
-
-def rel_attention_mfma_wide_supported(dh: int) -> bool:
-    """Head widths of the matrix-core biased attention kernels that own 16 rows per workgroup
-    (``gn_rel_attention_mfma_wide_supported``): 64."""
-    return bool(_lib.lib().gn_rel_attention_mfma_wide_supported(int(dh)))
-
-
-def rel_attention_wide_shared_supported(dh: int) -> bool:
-    """Head widths of the two-lanes-per-query biased attention kernels that form ``s_ij`` once per pair for a group of heads
-    (``gn_rel_attention_wide_shared_supported``): 64."""
-    return bool(_lib.lib().gn_rel_attention_wide_shared_supported(int(dh)))
-
-
-# kernel family (the stem of its C entries) -> (what the message calls it, the head width it is built for, the type of its rows:
-# qkv, qp, out, u, dout, du and the gradients; xt, freq, lse2 are fp32 in every family)
+# The one description of the six families, and (rel_attention_family) the one place where one of them is chosen.
 _REL_FAMILY = {
-    "rel_attention": ("", 32, torch.float32),
-    "rel_attention_wide": (" (two lanes per query)", 64, torch.float32),
-    "rel_attention_shared": (" (s_ij shared by a group of heads)", 32, torch.float32),
-    "rel_attention_mfma": (" (bf16 operands on the matrix cores)", 32, torch.bfloat16),
-    "rel_attention_mfma_wide": (" (bf16 operands on the matrix cores, 16 rows per workgroup)", 64, torch.bfloat16),
-    "rel_attention_wide_shared": (" (two lanes per query, s_ij shared by a group of heads)", 64, torch.float32),
+    "rel_attention": _RelFamily("", 32, torch.float32, False, False, "head width 32, fp32, one lane per query"),
+    "rel_attention_wide": _RelFamily(" (two lanes per query)", 64, torch.float32, False, False,
+                                     "head width 64, fp32, two lanes hold one query"),
+    "rel_attention_shared": _RelFamily(" (s_ij shared by a group of heads)", 32, torch.float32, True, False,
+                                       "head width 32, fp32, the bits of ``rel_attention``: one workgroup serves 8 heads and "
+                                       "evaluates each pair's ``s_ij`` once for all of them"),
+    "rel_attention_mfma": _RelFamily(" (bf16 operands on the matrix cores)", 32, torch.bfloat16, False, True,
+                                     "head width 32, bf16 rows on the matrix cores: ``s_ij`` is formed in fp32 and rounded once "
+                                     "to bf16; softmax and accumulation are fp32"),
+    "rel_attention_mfma_wide": _RelFamily(" (bf16 operands on the matrix cores, 16 rows per workgroup)", 64, torch.bfloat16,
+                                          False, True, "head width 64, the types and rounding points of ``rel_attention_mfma``; "
+                                          "a workgroup owns 16 rows and two threads form each pair's ``s_ij``"),
+    "rel_attention_wide_shared": _RelFamily(" (two lanes per query, s_ij shared by a group of heads)", 64, torch.float32, True,
+                                            False, "head width 64, fp32, the bits of ``rel_attention_wide``: one workgroup "
+                                            "serves 4 heads and evaluates each pair's ``s_ij`` once for all of them"),
 }
 
 
+def rel_attention_family(dh: int, *, shared: bool = False, matrix: bool = False) -> Optional[str]:
+    """The kernel family (a key of ``_REL_FAMILY``) that runs the biased attention at head width ``dh``, or None where none is
+    built.  ``matrix``: bf16 rows on the matrix cores; ``shared``: ``s_ij`` once per pair for a group of heads.  ``matrix`` wins
+    over ``shared``."""
+    for stem, f in _REL_FAMILY.items():
+        if f.built == dh and f.matrix == bool(matrix) and f.shared == bool(shared and not matrix):
+            return stem
+    return None
+
+
 def _rel_check(qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, family: str) -> Tuple[int, int]:
-    what, built, rows = _REL_FAMILY[family]
+    f = _REL_FAMILY[family]
     for t, name in ((qkv, "qkv"), (qp, "qp")):
-        _need(t, rows, name)
+        _need(t, f.rows, name)
     for t, name in ((xt, "xt"), (freq, "freq")):
         _need(t, torch.float32, name)
     N, d = int(qp.shape[0]), int(qp.shape[1])
@@ -1447,13 +1443,17 @@ def _rel_check(qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, f
         raise ValueError("need qkv [N, 3*d], qp [N, d] with d a multiple of the number of heads, xt [N, >= 4]")
     dh = d // n_head
     if not getattr(_lib.lib(), f"gn_{family}_supported")(dh):
-        raise NotImplementedError(f"biased ragged attention{what}: head width {dh} is not built ({built} is); no fallback")
+        raise NotImplementedError(f"biased ragged attention{f.what}: head width {dh} is not built ({f.built} is); no fallback")
     if int(freq.numel()) != dh // 2 or not freq.is_contiguous():
         raise ValueError("freq must hold dh / 2 contiguous frequencies")
     return N, d
 
 
-def _rel_fwd(qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, ptr: Tensor, plan: Tensor, family: str):
+def rel_attention_run_fwd(family: str, qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, ptr: Tensor, plan: Tensor):
+    """Ragged attention with the spacetime bias of ``DeepIce`` recomputed per pair, on kernel family ``family``
+    (``gn_<family>_fwd``): scores ``q k / sqrt(dh) + qp . s_ij``, ``s_ij`` the sinusoidal embedding of the clipped 4-distance of
+    pulses ``i``, ``j`` (columns 0-3 of ``xt``: x, y, z, time).  ``qkv``, ``qp`` and the results have the family's row type.
+    -> (out ``[N, d]`` = sum_j a_ij v_j, u ``[N, d]`` = sum_j a_ij s_ij, lse2 ``[N, H]`` fp32)."""
     N, d = _rel_check(qkv, qp, xt, freq, n_head, family)
     B = int(ptr.shape[0]) - 1
     out = torch.empty((N, d), dtype=qkv.dtype, device=qkv.device)
@@ -1467,8 +1467,10 @@ def _rel_fwd(qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, ptr
     return out, u, lse2
 
 
-def _rel_bwd(qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, ptr: Tensor, plan: Tensor, out: Tensor, u: Tensor,
-             lse2: Tensor, dout: Tensor, du: Tensor, family: str) -> Tuple[Tensor, Tensor]:
+def rel_attention_run_bwd(family: str, qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, ptr: Tensor, plan: Tensor,
+                          out: Tensor, u: Tensor, lse2: Tensor, dout: Tensor, du: Tensor) -> Tuple[Tensor, Tensor]:
+    """Gradients of :func:`rel_attention_run_fwd` on the same family (``gn_<family>_bwd``; ``dout``, ``du`` of the family's row
+    type) -> (dqkv ``[N, 3 d]``, dqp ``[N, d]``), of that type; ``xt`` carries none."""
     N, d = _rel_check(qkv, qp, xt, freq, n_head, family)
     for t, name in ((out, "out"), (u, "u"), (dout, "dout"), (du, "du")):
         _need(t, qkv.dtype, name)
@@ -1487,80 +1489,42 @@ def _rel_bwd(qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, ptr
     return dqkv, dqp
 
 
-def rel_attention_fwd(qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, ptr: Tensor, plan: Tensor):
-    """Ragged attention with the spacetime bias of ``DeepIce`` recomputed per pair (``gn_rel_attention_fwd``): scores
-    ``q k / sqrt(dh) + qp . s_ij``, ``s_ij`` the sinusoidal embedding of the clipped 4-distance of pulses ``i``, ``j`` (columns
-    0-3 of ``xt``: x, y, z, time).  fp32.  -> (out ``[N, d]`` = sum_j a_ij v_j, u ``[N, d]`` = sum_j a_ij s_ij, lse2 ``[N, H]``)."""
-    return _rel_fwd(qkv, qp, xt, freq, n_head, ptr, plan, "rel_attention")
+def _rel_named(stem: str, which: str):
+    """The public function ``<stem>_<which>`` of one family: the generic call with the family fixed."""
+    f = _REL_FAMILY[stem]
+    if which == "supported":
+        def fn(dh: int) -> bool:
+            return bool(getattr(_lib.lib(), f"gn_{stem}_supported")(int(dh)))
+        doc = f"Head widths of the ``{stem}`` kernels (``gn_{stem}_supported``): {f.built}.  The family: {f.doc}."
+    else:
+        run = rel_attention_run_fwd if which == "fwd" else rel_attention_run_bwd
+
+        def fn(*args, **kwargs):
+            return run(stem, *args, **kwargs)
+        doc = f":func:`rel_attention_run_{which}` on ``gn_{stem}_{which}``: {f.doc}."
+    fn.__name__ = fn.__qualname__ = f"{stem}_{which}"
+    fn.__doc__ = doc
+    return fn
 
 
-def rel_attention_bwd(qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, ptr: Tensor, plan: Tensor,
-                      out: Tensor, u: Tensor, lse2: Tensor, dout: Tensor, du: Tensor) -> Tuple[Tensor, Tensor]:
-    """Gradients of :func:`rel_attention_fwd` -> (dqkv ``[N, 3 d]``, dqp ``[N, d]``); ``xt`` carries none."""
-    return _rel_bwd(qkv, qp, xt, freq, n_head, ptr, plan, out, u, lse2, dout, du, "rel_attention")
-
-
-def rel_attention_wide_fwd(qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, ptr: Tensor, plan: Tensor):
-    """:func:`rel_attention_fwd` for head width 64 (``gn_rel_attention_wide_fwd``: two lanes hold one query)."""
-    return _rel_fwd(qkv, qp, xt, freq, n_head, ptr, plan, "rel_attention_wide")
-
-
-def rel_attention_wide_bwd(qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, ptr: Tensor, plan: Tensor,
-                           out: Tensor, u: Tensor, lse2: Tensor, dout: Tensor, du: Tensor) -> Tuple[Tensor, Tensor]:
-    """Gradients of :func:`rel_attention_wide_fwd` (``gn_rel_attention_wide_bwd``) -> (dqkv ``[N, 3 d]``, dqp ``[N, d]``)."""
-    return _rel_bwd(qkv, qp, xt, freq, n_head, ptr, plan, out, u, lse2, dout, du, "rel_attention_wide")
-
-
-def rel_attention_shared_fwd(qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, ptr: Tensor, plan: Tensor):
-    """:func:`rel_attention_fwd` (head width 32, the same bits) on ``gn_rel_attention_shared_fwd``: one workgroup serves 8 heads
-    and evaluates each pair's ``s_ij`` once for all of them."""
-    return _rel_fwd(qkv, qp, xt, freq, n_head, ptr, plan, "rel_attention_shared")
-
-
-def rel_attention_shared_bwd(qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, ptr: Tensor, plan: Tensor,
-                             out: Tensor, u: Tensor, lse2: Tensor, dout: Tensor, du: Tensor) -> Tuple[Tensor, Tensor]:
-    """Gradients of :func:`rel_attention_shared_fwd` (``gn_rel_attention_shared_bwd``) -> (dqkv ``[N, 3 d]``, dqp ``[N, d]``)."""
-    return _rel_bwd(qkv, qp, xt, freq, n_head, ptr, plan, out, u, lse2, dout, du, "rel_attention_shared")
-
-
-def rel_attention_mfma_fwd(qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, ptr: Tensor, plan: Tensor):
-    """:func:`rel_attention_fwd` (head width 32) with bf16 operands on the matrix cores (``gn_rel_attention_mfma_fwd``): ``qkv``,
-    ``qp`` and the results ``out``, ``u`` are bf16, ``xt``, ``freq`` and ``lse2`` fp32.  ``s_ij`` is formed in fp32 and rounded once to
-    bf16; softmax and accumulation are fp32."""
-    return _rel_fwd(qkv, qp, xt, freq, n_head, ptr, plan, "rel_attention_mfma")
-
-
-def rel_attention_mfma_bwd(qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, ptr: Tensor, plan: Tensor,
-                           out: Tensor, u: Tensor, lse2: Tensor, dout: Tensor, du: Tensor) -> Tuple[Tensor, Tensor]:
-    """Gradients of :func:`rel_attention_mfma_fwd` (``gn_rel_attention_mfma_bwd``; ``dout``, ``du`` bf16) -> (dqkv ``[N, 3 d]``,
-    dqp ``[N, d]``), both bf16."""
-    return _rel_bwd(qkv, qp, xt, freq, n_head, ptr, plan, out, u, lse2, dout, du, "rel_attention_mfma")
-
-
-def rel_attention_mfma_wide_fwd(qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, ptr: Tensor, plan: Tensor):
-    """:func:`rel_attention_mfma_fwd` for head width 64 (``gn_rel_attention_mfma_wide_fwd``): the same types and rounding points;
-    a workgroup owns 16 rows and two threads form each pair's ``s_ij``."""
-    return _rel_fwd(qkv, qp, xt, freq, n_head, ptr, plan, "rel_attention_mfma_wide")
-
-
-def rel_attention_mfma_wide_bwd(qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, ptr: Tensor, plan: Tensor,
-                                out: Tensor, u: Tensor, lse2: Tensor, dout: Tensor, du: Tensor) -> Tuple[Tensor, Tensor]:
-    """Gradients of :func:`rel_attention_mfma_wide_fwd` (``gn_rel_attention_mfma_wide_bwd``; ``dout``, ``du`` bf16) -> (dqkv
-    ``[N, 3 d]``, dqp ``[N, d]``), both bf16."""
-    return _rel_bwd(qkv, qp, xt, freq, n_head, ptr, plan, out, u, lse2, dout, du, "rel_attention_mfma_wide")
-
-
-def rel_attention_wide_shared_fwd(qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, ptr: Tensor, plan: Tensor):
-    """:func:`rel_attention_wide_fwd` (head width 64, the same bits) on ``gn_rel_attention_wide_shared_fwd``: one workgroup serves
-    4 heads and evaluates each pair's ``s_ij`` once for all of them."""
-    return _rel_fwd(qkv, qp, xt, freq, n_head, ptr, plan, "rel_attention_wide_shared")
-
-
-def rel_attention_wide_shared_bwd(qkv: Tensor, qp: Tensor, xt: Tensor, freq: Tensor, n_head: int, ptr: Tensor, plan: Tensor,
-                                  out: Tensor, u: Tensor, lse2: Tensor, dout: Tensor, du: Tensor) -> Tuple[Tensor, Tensor]:
-    """Gradients of :func:`rel_attention_wide_shared_fwd` (``gn_rel_attention_wide_shared_bwd``) -> (dqkv ``[N, 3 d]``,
-    dqp ``[N, d]``)."""
-    return _rel_bwd(qkv, qp, xt, freq, n_head, ptr, plan, out, u, lse2, dout, du, "rel_attention_wide_shared")
+rel_attention_supported = _rel_named("rel_attention", "supported")
+rel_attention_fwd = _rel_named("rel_attention", "fwd")
+rel_attention_bwd = _rel_named("rel_attention", "bwd")
+rel_attention_wide_supported = _rel_named("rel_attention_wide", "supported")
+rel_attention_wide_fwd = _rel_named("rel_attention_wide", "fwd")
+rel_attention_wide_bwd = _rel_named("rel_attention_wide", "bwd")
+rel_attention_shared_supported = _rel_named("rel_attention_shared", "supported")
+rel_attention_shared_fwd = _rel_named("rel_attention_shared", "fwd")
+rel_attention_shared_bwd = _rel_named("rel_attention_shared", "bwd")
+rel_attention_mfma_supported = _rel_named("rel_attention_mfma", "supported")
+rel_attention_mfma_fwd = _rel_named("rel_attention_mfma", "fwd")
+rel_attention_mfma_bwd = _rel_named("rel_attention_mfma", "bwd")
+rel_attention_mfma_wide_supported = _rel_named("rel_attention_mfma_wide", "supported")
+rel_attention_mfma_wide_fwd = _rel_named("rel_attention_mfma_wide", "fwd")
+rel_attention_mfma_wide_bwd = _rel_named("rel_attention_mfma_wide", "bwd")
+rel_attention_wide_shared_supported = _rel_named("rel_attention_wide_shared", "supported")
+rel_attention_wide_shared_fwd = _rel_named("rel_attention_wide_shared", "fwd")
+rel_attention_wide_shared_bwd = _rel_named("rel_attention_wide_shared", "bwd")
 
 
 # ------------------------------------------------------------------------------ TAGConv (ConvNet)

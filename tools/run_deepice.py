@@ -54,9 +54,9 @@ if HEAD not in (32, 64):
     sys.exit("--head-size: 32 or 64")
 WIDE = HEAD == 64
 g.Attention_rel.shared_bias = SHARED
-rel_fwd, rel_bwd = (ops.rel_attention_wide_fwd, ops.rel_attention_wide_bwd) if WIDE else (ops.rel_attention_fwd, ops.rel_attention_bwd)
-REL = "rel_attention_wide" if WIDE else "rel_attention"
-REL_SHARED = "rel_attention_wide_shared" if WIDE else "rel_attention_shared"
+REL = ops.rel_attention_family(HEAD)
+REL_SHARED = ops.rel_attention_family(HEAD, shared=True)
+rel_fwd, rel_bwd = getattr(ops, REL + "_fwd"), getattr(ops, REL + "_bwd")
 B = int(argv[1]) if len(argv) > 1 else 1024
 dtype = argv[2] if len(argv) > 2 else "bf16"
 steps = int(argv[3]) if len(argv) > 3 else 10
@@ -131,7 +131,7 @@ if SHARED or (MATRIX and not WIDE):
 if MATRIX:
     bf = torch.bfloat16
     qkv_b, qp_b, dout_b, du_b = qkv.to(bf), qp.to(bf), dout.to(bf), du.to(bf)
-    MFMA = "rel_attention_mfma_wide" if WIDE else "rel_attention_mfma"
+    MFMA = ops.rel_attention_family(HEAD, matrix=True)
     mfma_fwd, mfma_bwd = getattr(ops, MFMA + "_fwd"), getattr(ops, MFMA + "_bwd")
     out_b, u_b, lse2_b = mfma_fwd(qkv_b, qp_b, xt, freq, H, ptr32, plan)
     pieces[MFMA + "_fwd"] = timed(lambda: mfma_fwd(qkv_b, qp_b, xt, freq, H, ptr32, plan))
